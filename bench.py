@@ -18,6 +18,10 @@ Launch forms (both are tested):
     python bench.py --gpus N ...                      WORLD_SIZE unset: bench.py starts its N ranks itself (one process per GPU, rendezvous on 127.0.0.1:free port)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
+A plain run sets up, warms up, times --steps steps and prints the ONE JSON line (metric, value, unit, ms_per_step, ...); --full adds every other measurement of the
+report (loader timings, the round evaluation kernel's probe and roofline, the legs after the timed region, the .wtns emission, the CPU baseline).  --dump-outputs DIR
+writes what the last timed step computed (dump_outputs).
+
 Structure: `ServiceLoop` is the loop (calculators, streams, pinned inputs, counters); every leg of the report is a function that takes it.
 """
 import argparse
@@ -29,7 +33,10 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")     # every stream of the job needs its own hardware queue (ROCm default: 4); libpob_hip.so refuses the pipeline below 12
+# every stream of the job needs its own hardware queue (ROCm default: 4); libpob_hip.so refuses the pipeline below 12, so a smaller value inherited from the
+# environment is raised before the HIP runtime reads it
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 12:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 MAIN = "ProofOfBurn(16, 4, 16, 50, 31, 2, 10 ** 19, 10 ** 20)"      # circuits/main_proof_of_burn.circom:27
 HBM_PEAK_GBS = 8000.0                                                # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
@@ -123,6 +130,11 @@ def parse_args(argv=None):
     ap.add_argument("--shim", action="store_true", help="TESTS ONLY: run the loop on the CPU shim of the kernels (tests/hostsim) -- no GPU, no timing claims, no roofline; "
                                                         "exercises the multi-rank plumbing (slices, pinned buffers, loader width, the records' all-gather) under gloo")
     ap.add_argument("--dump-results", default=None, help="rank 0 writes the gathered records of the LAST batch (uint8 [N*B, 44]) to this .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64): the batch's "
+                                                                         "records and a seeded sample of wires of a few of its witnesses (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline: the native / Python loader timings and their cross-check, the probe of "
+                                                        "the round evaluation kernel, the legs after the timed region, the roofline, the .wtns emission, the single-witness latency "
+                                                        "and the CPU baseline (the --no-* options and --other-depths / --probe-after select among them)")
     return ap.parse_args(argv)
 
 
@@ -670,6 +682,36 @@ def leg_single_witness_latency(job):
             "ms_total": round((best[0] + best[1]) * 1e3, 2), "commitment": str(best[3])}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs: what the last timed step computed
+DUMP_SEED, DUMP_WITNESSES, DUMP_WIRES = 0x5EED, 4, 2048
+
+
+def _bits(np, u8):
+    """uint8 [..., n] little-endian bytes -> float32 [..., 8 n], one bit per value (bit 0 of byte 0 first): exact in float32, and a difference is a whole 1.0"""
+    return np.unpackbits(u8, axis=-1, bitorder="little").astype(np.float32)
+
+
+def dump_outputs(out_dir, rec, calc):
+    """rec: uint8 [GB, 44] records of the last timed batch (every rank's at N > 1), the arrays the service loop hands its caller; calc: the calculator that computed this
+    rank's slice of that batch, whose resident vector still holds it.  Writes status, check_status, bad_wire (float64 [GB]) and commitment_bits (float32 [GB, 256]);
+    and, expanded from the resident vector as the .wtns emitter does, the canonical values of wire 0 and DUMP_WIRES - 1 other wires of DUMP_WITNESSES witnesses of
+    the slice, all chosen by DUMP_SEED: witness_sample_bits (float32 [witnesses, wires, 256]), named by witness_sample_witnesses / witness_sample_wires (float64)."""
+    np = __import__("numpy")
+    from proof_of_burn_amd import RECORD_DTYPE
+    r = np.ascontiguousarray(rec, dtype=np.uint8).view(RECORD_DTYPE).reshape(-1)
+    rng = np.random.default_rng(DUMP_SEED)
+    wits = np.sort(rng.choice(calc.n, size=min(DUMP_WITNESSES, calc.n), replace=False))
+    wires = np.concatenate([[0], 1 + np.sort(rng.choice(calc.nwitness - 1, size=min(DUMP_WIRES, calc.nwitness) - 1, replace=False))]).astype(np.uint32)
+    sample = np.stack([calc.witness_payload_reduced(int(w), wires).reshape(-1, 32) for w in wits])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"status": r["status"].astype(np.float64), "check_status": r["check_status"].astype(np.float64), "bad_wire": r["bad_wire"].astype(np.float64),
+              "commitment_bits": _bits(np, r["commitment"]), "witness_sample_bits": _bits(np, sample),
+              "witness_sample_witnesses": wits.astype(np.float64), "witness_sample_wires": wires.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     args = parse_args()
@@ -704,15 +746,20 @@ def main():
     texts = [TextBatch([json.dumps(inp).encode() for inp in bt.inputs]) for bt in batches]
     pinned = [PinnedInputs(calc0, B) for _ in range(NB)]
     calc0.pack_json(texts[0], out=pinned[0])            # (first call: the loader pool's threads start, first touch of the texts)
-    t0 = time.time()
-    for rep in range(3):
-        for b in range(NB):
+    t_pack_native = t_pack_py = None
+    if not args.full:
+        for b in range(1, NB):
             calc0.pack_json(texts[b], out=pinned[b])
-    t_pack_native = (time.time() - t0) / (3 * NB)
-    t0 = time.time()
-    ref = calc0.pack(batches[0].inputs[:min(B, 128)])
-    t_pack_py = (time.time() - t0) / min(B, 128) * B
-    assert all(np.array_equal(x, y[:min(B, 128)]) for x, y in zip(ref, (pinned[0].fr, pinned[0].widened(), pinned[0].forced))), "native loader differs from the Python loader"
+    else:
+        t0 = time.time()
+        for rep in range(3):
+            for b in range(NB):
+                calc0.pack_json(texts[b], out=pinned[b])
+        t_pack_native = (time.time() - t0) / (3 * NB)
+        t0 = time.time()
+        ref = calc0.pack(batches[0].inputs[:min(B, 128)])
+        t_pack_py = (time.time() - t0) / min(B, 128) * B
+        assert all(np.array_equal(x, y[:min(B, 128)]) for x, y in zip(ref, (pinned[0].fr, pinned[0].widened(), pinned[0].forced))), "native loader differs from the Python loader"
     expect = [_expect(np, bt) for bt in batches]
     loop.set_inputs(pinned, expect)
 
@@ -724,7 +771,7 @@ def main():
     if args.warmup:
         loop.run(args.warmup)
     job.fence()
-    if not args.probe_after and loop.fetch_each:
+    if args.full and not args.probe_after and loop.fetch_each:
         loop.probe(True)
     loop.reset_counters()
     t0 = time.perf_counter()
@@ -734,8 +781,11 @@ def main():
     assert loop.validated == args.steps * B, "not every batch was validated inside the timed region"
     host_ms = {k: round(v / args.steps * 1e3, 3) for k, v in loop.host_s.items()}
     validated_timed, h2d_per_step = loop.validated, loop.h2d_bytes // max(args.steps, 1)
+    if args.dump_outputs and rank == 0:
+        last_c = (args.warmup + args.steps - 1) % NC           # the calculator of the last timed step (ServiceLoop.run)
+        dump_outputs(args.dump_outputs, (loop.last_gather if world > 1 else loop.recs[last_c]).cpu().numpy(), loop.calcs[last_c])
     probe_steps = 0
-    if args.probe_after and loop.fetch_each:
+    if args.full and args.probe_after and loop.fetch_each:
         # the dominant kernel as it runs IN the service loop: the same loop for a few more batches with HIP events around each of its launches
         loop.probe(True)
         probe_steps = 16
@@ -758,16 +808,16 @@ def main():
         np.save(args.dump_results, loop.recs[last_k % NC].cpu().numpy())
     ms_step = dt / args.steps * 1e3
 
-    # ---- legs after the timed region, same run, same box
+    # ---- legs after the timed region, same run, same box (--full)
     e2e = bare = single = tracks_pipeline = None
-    if PIPE and INORDER and not args.no_single and loop.fetch_each:
+    if args.full and PIPE and INORDER and not args.no_single and loop.fetch_each:
         e2e = leg_e2e_from_json(job, loop, texts, max(args.steps, 40), ms_step)
-    if PIPE and not args.no_single and loop.fetch_each:
+    if args.full and PIPE and not args.no_single and loop.fetch_each:
         bare = leg_kernel_pipeline_only(job, loop)
-    if PIPE and not args.no_single:
+    if args.full and PIPE and not args.no_single:
         single, tracks_pipeline = legs_track_schedule(job, loop)
     depths, depth16, strong_slice, separate_eval = {}, None, None, None
-    lone = rank == 0 and world == 1 and not job.strong and not args.no_extra_legs and loop.fetch_each and not args.shim and args.main == "proof_of_burn"
+    lone = args.full and rank == 0 and world == 1 and not job.strong and not args.no_extra_legs and loop.fetch_each and not args.shim and args.main == "proof_of_burn"
     if lone and INORDER and PIPE:
         for d in [int(x) for x in args.other_depths.split(",") if x.strip()]:
             if d != NC and d >= 2:
@@ -799,10 +849,10 @@ def main():
                                          "h2d_bytes_per_step": int(h2d_per_step), "calculators_in_flight": NC, "bound_cpus": (len(job.bound_cpus) if job.bound_cpus else None),
                                          "loader_threads_env": os.environ.get("POB_LOADER_THREADS"), "dist_backend": job.backend}}), flush=True)
     else:
-        roofline = leg_roofline(job, loop, info, kchk_in_step, ms_step, probe_steps)
-        emission = leg_emission(calc0, info) if rank == 0 and not args.no_emission else None
-        latency = leg_single_witness_latency(job) if rank == 0 and world == 1 and not args.no_emission else None
-        cpu = cpu_baseline(batches[0], info, args.cpu_samples) if rank == 0 and world == 1 and not args.no_cpu_baseline else None
+        roofline = leg_roofline(job, loop, info, kchk_in_step, ms_step, probe_steps) if args.full else None
+        emission = leg_emission(calc0, info) if args.full and rank == 0 and not args.no_emission else None
+        latency = leg_single_witness_latency(job) if args.full and rank == 0 and world == 1 and not args.no_emission else None
+        cpu = cpu_baseline(batches[0], info, args.cpu_samples) if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline else None
         if rank == 0:
             line = {
                 "metric": "proof_of_burn witnesses/sec", "value": round(GB * args.steps / dt, 1), "unit": "witnesses/s", "n_gpus": world, "steps": args.steps,
@@ -829,9 +879,9 @@ def main():
                            "validated_witnesses": validated_timed, "h2d_bytes_per_step": int(h2d_per_step),
                            "rccl_ranks": ranks["rccl_ranks"], "dist_backend": job.backend,
                            "input_synthesis_s_per_batch": round(t_synth, 2), "host_ms_per_step": host_ms,
-                           "json_to_packed_witnesses_per_s": round(B / max(t_pack_native, 1e-9), 1),
+                           "json_to_packed_witnesses_per_s": round(B / max(t_pack_native, 1e-9), 1) if args.full else None,
                            "json_to_packed": {"what": "input.json texts -> packed rows (byte form) in pinned memory, pob_pack_json_batch8 on the persistent loader pool (bit-equal to the Python loader on a sample of this batch)",
-                                              "host_cores": os.cpu_count(), "python_loader_witnesses_per_s_one_core": round(B / max(t_pack_py, 1e-9), 1)}},
+                                              "host_cores": os.cpu_count(), "python_loader_witnesses_per_s_one_core": round(B / max(t_pack_py, 1e-9), 1)} if args.full else None},
                 "ranks": ranks,
                 "roofline": roofline, "cpu_baseline": cpu, "emission": emission, "single_calculator": single, "tracks_pipeline": tracks_pipeline, "kernel_pipeline_only": bare, "single_witness_latency": latency,
                 "depth16": depth16, "strong_slice": strong_slice, "other_depths": depths or None, "separate_evaluation_pass": separate_eval, "e2e_from_json": e2e,

@@ -284,6 +284,43 @@ def test_bench_py_starts_its_own_ranks_without_a_launcher():
     assert bad.returncode != 0
 
 
+@pytest.mark.timeout(600)
+def test_bench_py_dumps_the_outputs_of_its_last_timed_step():
+    """`bench.py --dump-outputs DIR` on the CPU shim: the records of the last timed batch (status, verdicts, commitment bits) and a seeded sample of wires of a few of
+    its witnesses, as float .npy files within 64 MB; a second run with the same arguments writes the same arrays, the commitments are the last batch's and the
+    sampled wires equal the CPU oracle's witness"""
+    import tempfile
+    import numpy as np
+    from proof_of_burn_amd import inputs as gen
+    from tests import oracle_ffi as O
+    from tests.hostsim import build as hb
+    hb.build()
+    B, steps, warmup, nb = 32, 3, 1, 4
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--shim", "--main", "spend", "--steps", str(steps), "--warmup", str(warmup), "--batch", str(B),
+           "--pipeline", "2", "--distinct-batches", str(nb)]
+    dumps = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i in range(2):
+            out = os.path.join(tmp, f"run{i}")
+            r = subprocess.run(cmd + ["--dump-outputs", out], env=env, capture_output=True, text=True, cwd=ROOT, timeout=500)
+            assert r.returncode == 0, r.stderr[-3000:]
+            dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["bad_wire", "check_status", "commitment_bits", "status", "witness_sample_bits", "witness_sample_wires", "witness_sample_witnesses"]
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    batch = gen.synthetic_spend_batch(B, first=((warmup + steps - 1) % nb) * B)
+    assert a["status"].shape == (B,) and not a["status"].any() and (a["check_status"] == 0xFFFFFFFF).all() and (a["bad_wire"] == 0xFFFFFFFF).all()
+    assert [int.from_bytes(np.packbits(x.astype(np.uint8), bitorder="little").tobytes(), "little") for x in a["commitment_bits"]] == batch.commitments
+    wires = a["witness_sample_wires"].astype(np.int64)
+    assert wires[0] == 0 and len(a["witness_sample_witnesses"]) == 4
+    for w, got in zip(a["witness_sample_witnesses"].astype(np.int64), a["witness_sample_bits"]):
+        ref = O.run("Spend(31)", batch.inputs[w]).witness_numpy().reshape(-1, 32)[wires]
+        assert np.array_equal(np.packbits(got.astype(np.uint8), axis=-1, bitorder="little"), ref), int(w)
+
+
 def test_init_refuses_a_job_without_a_port(monkeypatch):
     """the ranks of one job must agree on the rendezvous port: it comes from the launcher (torch.distributed.run / MASTER_PORT), never from a default"""
     monkeypatch.setenv("WORLD_SIZE", "2"); monkeypatch.setenv("RANK", "0"); monkeypatch.delenv("MASTER_PORT", raising=False)

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out
 for r in $(seq 1 ${ROUNDS:-1}); do
   for v in "$@"; do
     L=${v%%:*}; A=${v#*:}
-    timeout 180 python bench.py --gpus 1 --steps ${STEPS:-96} --warmup ${WARMUP:-12} --no-cpu-baseline --no-emission --no-single --no-extra-legs $A > $R/ab_${L}_$r.json 2> $R/ab_${L}_$r.err
+    timeout 180 python bench.py --full --gpus 1 --steps ${STEPS:-96} --warmup ${WARMUP:-12} --no-cpu-baseline --no-emission --no-single --no-extra-legs $A > $R/ab_${L}_$r.json 2> $R/ab_${L}_$r.err
     python - <<PY
 import json
 try:

@@ -7,6 +7,6 @@ for LP in $LIBS; do
   L=${LP%%=*}; P=${LP#*=}
   if [ -n "$P" ]; then export POB_LIB_PATH=$GRAFT_REPO_ROOT/$P; else unset POB_LIB_PATH; fi
   for N in ${DEPTHS:-4 8}; do
-    timeout 180 python bench.py --gpus 1 --steps ${STEPS:-96} --warmup 12 --pipeline $N --no-cpu-baseline --no-emission --no-single --no-extra-legs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); r=d['roofline']; print('round $r $L N=$N', d['ms_per_step'], 'ms/step; round evaluation in the step', r['avg_ms'], 'ms = frac', r['frac'], '; whole evaluation alone', r['check_pass']['ms'], 'ms')"
+    timeout 180 python bench.py --full --gpus 1 --steps ${STEPS:-96} --warmup 12 --pipeline $N --no-cpu-baseline --no-emission --no-single --no-extra-legs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); r=d['roofline']; print('round $r $L N=$N', d['ms_per_step'], 'ms/step; round evaluation in the step', r['avg_ms'], 'ms = frac', r['frac'], '; whole evaluation alone', r['check_pass']['ms'], 'ms')"
   done
 done; done 2>&1 | tee gpurun_out/ab_libs_${TAG:-x}.txt

@@ -8,7 +8,7 @@ for r in 1 2; do
   pt 12:1 none; pt 12:1 parity; pt 12:1 quarters; pt 12:1 halves; pt 8:1 none; pt 8:1 parity; pt 4:1 none; pt 4:1 quarters
 done 2>&1 | tee $R/ab_s11_cumask.txt
 for r in 1 2; do
-  timeout 300 python bench.py --gpus 1 --steps 96 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s11_e2e_$r.json 2> $R/s11_e2e_$r.err
+  timeout 300 python bench.py --full --gpus 1 --steps 96 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s11_e2e_$r.json 2> $R/s11_e2e_$r.err
   python -c "
 import json
 d = json.loads(open('gpurun_out/s11_e2e_$r.json').read().strip().splitlines()[-1]); e = d['e2e_from_json']

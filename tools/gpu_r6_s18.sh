@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out
 timeout 200 python tools/loader_rate.py 1024 1,8,12,16,20,24,32,48 2>&1 | tail -10 | tee $R/s18_loader_rate.txt
 run() { # label env...
   L=$1; shift
-  env "$@" timeout 300 python bench.py --gpus 1 --steps 96 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s18_$L.json 2> $R/s18_$L.err
+  env "$@" timeout 300 python bench.py --full --gpus 1 --steps 96 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s18_$L.json 2> $R/s18_$L.err
   python -c "
 import json
 d = json.loads(open('gpurun_out/s18_$L.json').read().strip().splitlines()[-1]); e = d['e2e_from_json']

@@ -10,7 +10,7 @@ for M in 3 1; do
 done
 LIBS="new= r5=ab/libpob_r5.so" POINTS="4:0,8:0,12:0,4:1,8:1,12:1" ROUNDS=2 EXTRA="--alone" TAG=s5_loop bash tools/gpu_r6_ab.sh
 for N in 8 12 16; do
-  timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --pipeline $N --no-cpu-baseline > $R/s5_bench_driver_p$N.json 2> $R/s5_bench_driver_p$N.err
+  timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --pipeline $N --no-cpu-baseline > $R/s5_bench_driver_p$N.json 2> $R/s5_bench_driver_p$N.err
   python -c "
 import json
 d = json.loads(open('gpurun_out/s5_bench_driver_p$N.json').read().strip().splitlines()[-1])

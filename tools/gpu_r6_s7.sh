@@ -8,7 +8,7 @@ hipcc --offload-arch=gfx950 -O3 -w -I proof_of_burn_amd/csrc tools/ubench/fr_mul
 (cd /tmp && POB_PMC_INORDER=3 timeout 300 rocprofv3 --kernel-trace -d $R/s7_lone -o s -- python $GRAFT_REPO_ROOT/tools/pmc_one_batch.py > $R/s7_lone.log 2>&1)
 python tools/lone_batch_trace.py $R/s7_lone/s_results.db > $R/s7_lone_batch.txt 2>&1; rm -rf $R/s7_lone; cat $R/s7_lone_batch.txt | cut -c12-100
 timeout 300 python tools/unit_times.py 1024 > $R/s7_unit_times.txt 2>&1; awk '$3>0.04 || $2>0.04 || NR==1 || /F_|k_|all/' $R/s7_unit_times.txt
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $R/s7_bench_driver.json 2> $R/s7_bench_driver.err
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $R/s7_bench_driver.json 2> $R/s7_bench_driver.err
 python -c "
 import json
 d = json.loads(open('gpurun_out/s7_bench_driver.json').read().strip().splitlines()[-1])

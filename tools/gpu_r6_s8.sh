@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; mkdir -p gpurun_out; ulimit -c 0
 R=$GRAFT_REPO_ROOT/gpurun_out
 run() { # label env...
   L=$1; shift
-  env "$@" timeout 300 python bench.py --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s8_$L.json 2> $R/s8_$L.err
+  env "$@" timeout 300 python bench.py --full --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline --no-emission --no-extra-legs > $R/s8_$L.json 2> $R/s8_$L.err
   python -c "
 import json
 d = json.loads(open('gpurun_out/s8_$L.json').read().strip().splitlines()[-1]); e = d['e2e_from_json']

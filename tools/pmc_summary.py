@@ -34,7 +34,7 @@ def main(fetch_db, write_db, out):
     KCHK, KGEN = 4, 8                          # rounds per wavefront (keccak_kernels.hpp POB_KCHK_ROUNDS / POB_KGEN_ROUNDS)
     chunks = chk["grid_x_threads"] // 64       # (permutation, chunk) items of the evaluation launch
     res = {
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 1 --warmup 0 --batch %d" % (groups * 64),
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 1 --warmup 0 --batch %d" % (groups * 64),
         "groups": groups,
         "k_rounds_check": {"fetch_size_kb_raw": chk["avg_kb"], "hbm_read_bytes_per_launch": chk["avg_kb"] * 1024 * 2,
                            # every resident array of a chunk once: midRound[r0] + per round the 76 stored gate outputs and the stored midRound[r+1]
