@@ -286,8 +286,11 @@ int pob_debug_emit_counters(pob_handle h, uint64_t out[4], int reset);
 /* Test hook: the device code's two field inversions (the generator's / emitter's Kaliski almost-inverse and the emitter's Fermat fall-back) on n
  * canonical 32-byte LE inputs < p (0 -> 0), canonical outputs.                                                                          */
 int pob_debug_fr_inv(int device, const uint8_t* in, uint32_t n, uint8_t* out_kaliski, uint8_t* out_fermat);
+/* Test hook: fr_sqr(a) and fr_mul(a, a) of the device code on n 32-byte LE values a < p (Montgomery products: a * a * 2^-256 mod p); the two must be
+ * bit-equal.                                                                                                                          */
+int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr, uint8_t* out_mul);
 /* Test hook: storage class, rank within the class and wire index of a few named wires: "commitment"; "poseidon" (k-th wire of the
- * first Poseidon block); "pad.div.out" / "pad.div.rem" of KeccakBytes instance k (the Divide hint of divide.circom:23-24); ProofOfBurn only: "sc.exists" [k] of layer 1's SubstringCheck. */
+ * first Poseidon block), "poseidon.t3" / ".t4" / ".t5" (... of the first Poseidon block of width T = 3 / 4 / 5); "pad.div.out" / "pad.div.rem" of KeccakBytes instance k (the Divide hint of divide.circom:23-24); ProofOfBurn only: "sc.exists" [k] of layer 1's SubstringCheck. */
 int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k */
 
 /* Host helper used by the input producers (next row f1): Keccak-256 of a byte string.                           */

@@ -37,6 +37,13 @@ HD Fr fr_one_mont() { Fr r = {FR_R_LIMBS}; return r; }
 HD Fr fr_r2() { Fr r = {FR_R2_LIMBS}; return r; }
 HD Fr fr_zero() { Fr r = {{0, 0, 0, 0, 0, 0, 0, 0}}; return r; }
 
+// c ? a : b limb by limb (a select of the two values: `c ? a : b` on Fr lvalues may select an address, which sends the operands to scratch)
+HD Fr fr_sel(bool c, const Fr& a, const Fr& b) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = c ? a.l[i] : b.l[i];
+    return r;
+}
 HD bool fr_is_zero(const Fr& a) {
     uint32_t o = 0;
 #pragma unroll
@@ -96,7 +103,7 @@ HD Fr fr_neg(const Fr& a) { return fr_sub(fr_zero(), a); }
 #define FR_MADC(x, y) asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(acc), "+v"(hi) : "v"(x), "v"(y) : "vcc")
 #define FR_MADC_S(x, y) asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(acc), "+v"(hi) : "v"(x), "s"(y) : "vcc")
 // (splitting the a*b and m*p products over two accumulators to give a lone wavefront two dependency chains measured no faster)
-HDN Fr fr_mul(Fr a, Fr b) {
+HD Fr fr_mul_inl(Fr a, Fr b) {
     const uint32_t P[8] = FR_P_LIMBS;
     uint32_t m[8], t[9];
     uint64_t acc = 0; uint32_t hi = 0;
@@ -124,6 +131,7 @@ HDN Fr fr_mul(Fr a, Fr b) {
 }
 #undef FR_MADC
 #undef FR_MADC_S
+HDN Fr fr_mul(Fr a, Fr b) { return fr_mul_inl(a, b); }
 #else
 // Host (layout planner, tables): CIOS over 32-bit limbs.
 HDN Fr fr_mul(Fr a, Fr b) {
@@ -143,8 +151,59 @@ HDN Fr fr_mul(Fr a, Fr b) {
     for (int i = 0; i < 8; i++) r.l[i] = t[i];
     return (t[8] || fr_geq_p(r)) ? fr_sub_p(r) : r;
 }
+HD Fr fr_mul_inl(Fr a, Fr b) { return fr_mul(a, b); }
 #endif
-HD Fr fr_sqr(const Fr& a) { return fr_mul(a, a); }
+// Montgomery square a*a*2^-256 mod p, equal to fr_mul(a, a) for every a < p (both return the representative in [0, p)).
+// Product scanning as fr_mul, but column k takes each cross product a_i*a_j (i < j) once, in an accumulator of its own that
+// is doubled into the column, and the diagonal a_i*a_i once: 36 multiply-adds for a*a instead of 64 (m*p keeps its 64).
+// One body for device and host (the host build of the tests runs this same schedule): FR_SQ_MADC is the device fr_mul's
+// v_mad_u64_u32 + v_addc_co_u32 step on the device and the same 96-bit multiply-add in C elsewhere.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FR_SQ_MADC(lo, hi, x, y) asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(lo), "+v"(hi) : "v"(x), "v"(y) : "vcc")
+#define FR_SQ_MADC_S(lo, hi, x, y) asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(lo), "+v"(hi) : "v"(x), "s"(y) : "vcc")
+#else
+#define FR_SQ_MADC(lo, hi, x, y) do { const uint64_t pr_ = (uint64_t)(x) * (y); (lo) += pr_; (hi) += (lo) < pr_ ? 1u : 0u; } while (0)
+#define FR_SQ_MADC_S FR_SQ_MADC
+#endif
+// (c, ch) = 2 * sum a_i a_(k-i) over i0 <= i < k - i (< 2^67), added into the column
+#define FR_SQ_CROSS(k, i0) do { \
+        uint64_t c = 0; uint32_t ch = 0; \
+        _Pragma("unroll") for (int i = (i0); i < (k) - i; i++) FR_SQ_MADC(c, ch, a.l[i], a.l[(k) - i]); \
+        const uint64_t c2 = c << 1; const uint32_t ch2 = (ch << 1) | (uint32_t)(c >> 63); \
+        acc += c2; hi += ch2 + (acc < c2 ? 1u : 0u); } while (0)
+HD Fr fr_sqr_inl(Fr a) {
+    const uint32_t P[8] = FR_P_LIMBS;
+    uint32_t m[8], t[9];
+    uint64_t acc = 0; uint32_t hi = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (k > 0) FR_SQ_CROSS(k, 0);
+        if ((k & 1) == 0) FR_SQ_MADC(acc, hi, a.l[k >> 1], a.l[k >> 1]);
+#pragma unroll
+        for (int i = 0; i < k; i++) FR_SQ_MADC_S(acc, hi, m[i], P[k - i]);
+        m[k] = (uint32_t)acc * FR_NINV32;
+        FR_SQ_MADC_S(acc, hi, m[k], P[0]);
+        acc = (acc >> 32) | ((uint64_t)hi << 32); hi = 0;
+    }
+#pragma unroll
+    for (int k = 8; k < 16; k++) {
+        if (k < 14) FR_SQ_CROSS(k, k - 7);
+        if ((k & 1) == 0) FR_SQ_MADC(acc, hi, a.l[k >> 1], a.l[k >> 1]);
+#pragma unroll
+        for (int i = k - 7; i < 8; i++) FR_SQ_MADC_S(acc, hi, m[i], P[k - i]);
+        t[k - 8] = (uint32_t)acc;
+        acc = (acc >> 32) | ((uint64_t)hi << 32); hi = 0;
+    }
+    t[8] = (uint32_t)acc;
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = t[i];
+    return (t[8] || fr_geq_p(r)) ? fr_sub_p(r) : r;
+}
+#undef FR_SQ_CROSS
+#undef FR_SQ_MADC
+#undef FR_SQ_MADC_S
+HDN Fr fr_sqr(Fr a) { return fr_sqr_inl(a); }
 HD Fr fr_to_mont(const Fr& canon) { return fr_mul(canon, fr_r2()); }
 HD Fr fr_from_mont(const Fr& m) { Fr one = {{1, 0, 0, 0, 0, 0, 0, 0}}; return fr_mul(m, one); }
 // small signed integer -> Montgomery form (negative k -> p - |k|)

@@ -160,6 +160,14 @@ __global__ void k_fr_inv_test(const uint32_t* in, uint32_t* out_kaliski, uint32_
     const Fr a = fr_is_zero(x) ? fr_zero() : fr_from_mont(fr_inv(x)), b = fr_is_zero(x) ? fr_zero() : fr_from_mont(fr_inv_fermat(x));
     for (int j = 0; j < 8; j++) { out_kaliski[t * 8 + j] = a.l[j]; out_fermat[t * 8 + j] = b.l[j]; }
 }
+// test hook (pob_debug_fr_sqr): the device's Montgomery square and product of a value with itself on n inputs < p
+__global__ void k_fr_sqr_test(const uint32_t* in, uint32_t* out_sqr, uint32_t* out_mul, uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    Fr a; for (int j = 0; j < 8; j++) a.l[j] = in[t * 8 + j];
+    const Fr s = fr_sqr(a), m = fr_mul(a, a);
+    for (int j = 0; j < 8; j++) { out_sqr[t * 8 + j] = s.l[j]; out_mul[t * 8 + j] = m.l[j]; }
+}
 // ---- emit-time self-check (pob_emit_selfcheck): the relations of the DERIVED wires, evaluated on the canonical values as written into the emission window
 // (reference: circomlib comparators.circom IsZero `out <== -in*inv + 1; in*out === 0`, IsEqual `in[1] - in[0] ==> isz.in; isz.out ==> out`;
 //  substring_check.circom:45-49 `M[i+1] <== M[i] + mainInput[i] * 256^i`).  One thread per site; sites whose wires are not all inside the window are counted as
@@ -1910,6 +1918,22 @@ int pob_debug_fr_inv(int device, const uint8_t* in, uint32_t n, uint8_t* out_kal
     return rc;
 }
 
+// fr_sqr(a) and fr_mul(a, a) of the device code on n 32-byte LE values a < p (Montgomery in, Montgomery out: a * a * 2^-256 mod p)
+int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr, uint8_t* out_mul) {
+    if (!in || !out_sqr || !out_mul || n == 0) return POB_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return POB_E_HIP;
+    uint32_t *d_in = nullptr, *d_a = nullptr, *d_b = nullptr;
+    const size_t bytes = (size_t)n * 32;
+    int rc = POB_E_HIP;
+    if (hipMalloc(&d_in, bytes) == hipSuccess && hipMalloc(&d_a, bytes) == hipSuccess && hipMalloc(&d_b, bytes) == hipSuccess &&
+        hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_fr_sqr_test, dim3((n + 63) / 64), dim3(64), 0, 0, d_in, d_a, d_b, n);
+        if (hipMemcpy(out_sqr, d_a, bytes, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(out_mul, d_b, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = POB_OK;
+    }
+    if (d_in) hipFree(d_in); if (d_a) hipFree(d_a); if (d_b) hipFree(d_b);
+    return rc;
+}
+
 // which inverse paths of the emitter have run since the last reset (policy.hpp EmitP::ctr); the emission must be complete (pob_emit_next returned its last window)
 int pob_debug_emit_counters(pob_handle h, uint64_t out[4], int reset) {
     if (!h || !out) return POB_E_ARG;
@@ -1928,8 +1952,9 @@ int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t
     const Plan& pl = h->plan; const CircuitLayout& L = pl.L;
     const std::string n = name;
     auto set = [&](int c, uint64_t i, uint64_t w) { *cls = c; *index = i; *wire = w; return POB_OK; };
-    if (n == "poseidon") {            // k-th wire of the first Poseidon block (every wire of it is an FR wire)
-        for (const UnitDesc& u : pl.units) if (u.kind == CK_POS_SEG) {
+    if (n == "poseidon" || n == "poseidon.t3" || n == "poseidon.t4" || n == "poseidon.t5") {      // k-th wire of the first Poseidon block (of width T: ".tT"); every wire of it is an FR wire
+        const uint32_t want_t = n.size() > 8 ? (uint32_t)(n[10] - '0') : 0;
+        for (const UnitDesc& u : pl.units) if (u.kind == CK_POS_SEG && (want_t == 0 || u.a[0] == want_t)) {
             if (k >= pos_wires((int)u.a[0], pos_off((int)u.a[0]).rp)) return POB_E_ARG;
             return set(POB_CLASS_FR, u.cur.f + k, u.cur.w + k);
         }
