@@ -234,7 +234,8 @@ int pob_emit_queue(pob_handle h, uint32_t next_idx);
  * pob_emit_selfcheck_result, called when the emission is complete: relations checked, relations skipped (wires straddling two windows, dropped wires), and
  * the lowest wire whose relation does not hold (0xFFFFFFFF = none): of THIS emission -- while the check is on, pob_emit_queue does not pre-make the next
  * witness' window.  A witness emitted from a corrupted resident vector (pob_debug_poke of an operand) violates the relations of the derived wires that
- * consume the operand.                                                                                                                          */
+ * consume the operand.
+ * Packed emissions (pob_emit_begin_packed) are checked the same way, unchanged: the check reads the canonical window on the device, before the pack pass compacts it. */
 int pob_emit_selfcheck(pob_handle h, int enable);
 /* Reduced emissions: the class representative of every O0 wire under the map that will be emitted (alias[w] = the kept wire that stands for w, w itself if
  * it is kept; a wire pinned to the constant c < 2^30: -1 - c, to a larger constant: INT32_MIN; from circuit_model/o1.py O1Map), n_wires = n_witness.  With
@@ -248,6 +249,37 @@ int pob_emit_measure(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t 
 /* The same with an optional reduced map (keep != NULL: pob_emit_begin_reduced).  The first witness a handle emits at a window size
  * also allocates the window buffers (2 x device, 2 x pinned host) and runs the probe pass: call twice to separate that from the steady state. */
 int pob_emit_measure_ex(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, double* seconds, uint64_t* bytes);
+
+/* PACKED WINDOWS.  Replaces writeBinWitness (reference tests/test.py:36), which writes 32 bytes per wire: more than 97 % of a witness' values are the numbers 0 and 1, so a
+ * window crosses PCIe as 2-bit tags plus the values that are neither -- 36-100 x fewer bytes than the canonical window, whatever the payload (the encoding looks at values
+ * only).  The canonical window is expanded on the device as before; a pack pass (k_pack.hip) compacts it in front of the copy.  One packed window of n payload positions,
+ * all integers little-endian, every section on a 32-byte boundary, padding zero (format version 1):
+ *   header 32 B    u32 magic 'POBP', u32 version = 1, u64 first_wire, u32 n_wires, u32 n_small, u32 n_wide, u32 0
+ *   tag planes     ceil(n / 64) x {u64 lo, u64 hi}: bit i % 64 of pair i / 64 gives wire i's tag hi << 1 | lo.  0: the value 0; 1: the value 1; 2 ("small"): 2 <= value < 2^32;
+ *                  3 ("wide"): anything else, the 0xEE.. filler of a wire nobody owns included; bits beyond n are zero
+ *   chunk index    ceil(n / 4096) x {u32 small_before, u32 wide_before}: small / wide wires of this window in front of the chunk
+ *   small values   n_small x u32, wire order
+ *   wide values    n_wide x 32 bytes canonical LE, wire order
+ * pob_emit_begin_packed: keep == NULL (n_keep = 0): the O0 payload (pob_emit_begin); else the reduced one with the rules of pob_emit_begin_reduced (same map validation, same
+ * pinning through pob_reduced_map_pin, same refusal of a failed witness).  "Packed" is part of the payload kind: pob_emit_queue's pre-made first window is used only by a begin
+ * of the same kind, pob_emit_next after a packed begin is POB_E_STATE and so is pob_emit_next_packed after a canonical one.
+ * pob_emit_next_packed: the next packed window (`bytes` long, pinned host memory owned by the handle, valid until the following call); n_wires = 0 ends the witness.  The header,
+ * planes and index are copied with the window; the value sections cross inside this call, when the header's counts are on the host. */
+int pob_emit_begin_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires);
+int pob_emit_next_packed(pob_handle h, const uint8_t** data, uint64_t* bytes, uint64_t* first_wire, uint64_t* n_wires);
+/* Host only, no GPU touched: one packed window -> its n_wires canonical 32-byte values at dst (what writeBinWitness, reference tests/test.py:36, would have written for those
+ * wires).  Everything is validated before anything is written -- magic, version, the length recomputed from the header's counts, the chunk index and both counts against the
+ * planes' popcounts, tag bits beyond n, padding, every small value >= 2 and every wide value >= 2^32: POB_E_ARG on any inconsistency or a dst_cap below 32 * n_wires; hostile
+ * input is never read or written out of bounds.  threads: of the loader's persistent pool (0 = its width), work split by chunk.  Bounded by the 32 bytes per wire it writes:
+ * a consumer that wants more reads packed windows directly. */
+int pob_unpack_window(const uint8_t* packed, uint64_t packed_bytes, uint8_t* dst, uint64_t dst_cap, int threads);
+/* The .wtns file (pob_write_wtns for keep == NULL, pob_write_wtns_reduced otherwise: the same bytes) through the packed transfer and the host expansion. */
+int pob_write_wtns_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, const char* path);
+/* Measurement, as pob_emit_measure_ex: *seconds_pinned = `count` witnesses until their packed windows are in pinned memory, *d2h_bytes = the bytes that were copied
+ * device-to-host for them; dst != NULL: a second pass that also expands every window with pob_unpack_window(threads) into dst -- at its payload offset if dst_cap holds the
+ * whole payload, else (dst_cap >= one window) every window at dst -- gives *seconds_expanded. */
+int pob_emit_measure_packed(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
+                            double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes);
 
 /* Measurement: average duration (ms, HIP events on `stream`) of `iters` back-to-back launches of one kernel over
  * the current batch.  which: 0 = Keccak round expansion (generate), 1 = Keccak round constraint evaluation,

@@ -543,6 +543,14 @@ int pack_batch(const Shape& sh, const char* const* json, const uint64_t* len, ui
 }
 }  // namespace
 
+// the pool for the library's other host-side routines (pob_unpack_window, k_pack.hip)
+void pob_pool_run(uint32_t threads, const std::function<void(uint32_t)>& fn) {
+    LoaderPool& P = loader_pool();
+    std::lock_guard<std::mutex> lk(P.call_mu);
+    P.run(threads ? threads - 1 : 0, fn);
+}
+uint32_t pob_pool_width() { return default_threads(); }
+
 extern "C" {
 
 int pob_pack_json(int circuit, const uint64_t* params, int nparams, const char* json, uint64_t len, uint8_t* fr_row, int32_t* sm_row, uint32_t* forced, char* err, uint32_t errcap) {

@@ -15,6 +15,7 @@
 
 #include "../../include/pob_hip.h"
 #include "kernels_common.hpp"
+#include "pack_window.hpp"
 
 
 __global__ void k_init_invlut(uint32_t* lut) {   // canonical inverses of -4096..4096
@@ -363,6 +364,12 @@ struct pob_ctx {
         const int32_t* sc_alias = nullptr; uint64_t sc_alias_n = 0, sc_red_map = 0, sc_red_host_skipped = 0; uint32_t sc_red_nz = 0, sc_red_nm = 0;
         uint32_t *d_sc_zr = nullptr, *d_sc_mr = nullptr;
         bool red = false; uint64_t map_id = 0, total = 0; std::vector<uint32_t> keep; unsigned long long* d_rbits = nullptr; uint32_t* d_rpre = nullptr;
+        // packed windows (pob_emit_begin_packed, k_pack.hip): part of the payload KIND, like the map.  The pack pass turns the canonical window of a slot into d_pk[slot]; the header,
+        // tag planes and chunk index (a length the host knows) are copied with the window, the value sections when the caller takes the window and the header's counts are in
+        // pinned memory (s_val: the window copies queued on s_copy wait for expansions that have not run yet).  d_pk_blk / d_pk_tot: the scan's scratch, shared by the slots
+        // (every pack pass runs on the handle's own stream).  pk_d2h: bytes the packed emissions of this handle have copied to the host
+        bool packed = false, pre_made_packed = false; uint8_t* d_pk[NSLOT] = {nullptr, nullptr, nullptr}; uint32_t *d_pk_blk = nullptr, *d_pk_tot = nullptr; uint64_t pk_alloc_wires = 0, pk_d2h = 0;
+        hipStream_t s_val = nullptr;
     } em;
     // schedule
     std::vector<uint32_t> order;                       // unit indices grouped by (stage, lds flag)
@@ -863,7 +870,7 @@ void pob_close(pob_handle h) {
     if (!h) return;
     hipSetDevice(h->device);
     void* ptrs[] = {h->d_bits, h->d_sm, h->d_fr, h->d_units, h->d_order, h->d_L, h->d_sponges, h->d_perm_sponge, h->d_perm_block, h->d_pos,
-                    h->d_inv, h->d_pow256, h->d_ktab, h->d_emit_ctr, h->d_in_fr[0], h->d_in_fr[1], h->d_in_sm[0], h->d_in_sm[1], h->d_in_sm8[0], h->d_in_sm8[1], h->d_in_exc[0], h->d_in_exc[1], h->d_status_raw, h->d_status, h->d_chk, h->d_bad, h->d_outputs, h->d_records, h->em.d_win[0], h->em.d_win[1], h->em.d_win[2], h->em.d_order, h->em.d_probe, h->em.d_rbits, h->em.d_rpre, h->em.d_sc_z, h->em.d_sc_m, h->em.d_sc_c, h->em.d_sc_res, h->em.d_sc_zr, h->em.d_sc_mr};
+                    h->d_inv, h->d_pow256, h->d_ktab, h->d_emit_ctr, h->d_in_fr[0], h->d_in_fr[1], h->d_in_sm[0], h->d_in_sm[1], h->d_in_sm8[0], h->d_in_sm8[1], h->d_in_exc[0], h->d_in_exc[1], h->d_status_raw, h->d_status, h->d_chk, h->d_bad, h->d_outputs, h->d_records, h->em.d_win[0], h->em.d_win[1], h->em.d_win[2], h->em.d_order, h->em.d_probe, h->em.d_rbits, h->em.d_rpre, h->em.d_sc_z, h->em.d_sc_m, h->em.d_sc_c, h->em.d_sc_res, h->em.d_sc_zr, h->em.d_sc_mr, h->em.d_pk[0], h->em.d_pk[1], h->em.d_pk[2], h->em.d_pk_blk, h->em.d_pk_tot};
     for (void* p : ptrs) if (p) hipFree(p);
     for (int k = 0; k < pob_ctx::Emit::NSLOT; k++) {
         if (h->em.h_pin[k]) hipHostFree(h->em.h_pin[k]);
@@ -876,6 +883,7 @@ void pob_close(pob_handle h) {
     for (auto& pr : h->ev_kchk) for (hipEvent_t e : pr) if (e) hipEventDestroy(e);
     if (h->partner && h->partner->partner == h) h->partner->partner = nullptr;
     if (h->em.s_copy) hipStreamDestroy(h->em.s_copy);
+    if (h->em.s_val) hipStreamDestroy(h->em.s_val);
     if (h->pool) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         StreamPool* P = h->pool;
@@ -1381,9 +1389,14 @@ static int emit_make_window(pob_ctx* h, uint32_t idx, uint64_t k, int slot) {
         E.sc_checked += ncs;
     }
     HIPC(hipGetLastError());
+    if (E.packed) {           // behind everything that writes (and checks) the canonical window: compact it; what crosses now is the part whose length does not depend on the values
+        launch_pack_window(E.d_win[slot], w0, (uint32_t)wn, E.d_pk[slot], E.d_pk_blk, E.d_pk_tot, st);
+        HIPC(hipGetLastError());
+    }
     HIPC(hipEventRecord(E.ev_made[slot], st));
     HIPC(hipStreamWaitEvent(E.s_copy, E.ev_made[slot], 0));
-    HIPC(hipMemcpyAsync(E.h_pin[slot], E.d_win[slot], wn * 32, hipMemcpyDeviceToHost, E.s_copy));
+    if (E.packed) { HIPC(hipMemcpyAsync(E.h_pin[slot], E.d_pk[slot], pack_fixed_bytes(wn), hipMemcpyDeviceToHost, E.s_copy)); E.pk_d2h += pack_fixed_bytes(wn); }
+    else HIPC(hipMemcpyAsync(E.h_pin[slot], E.d_win[slot], wn * 32, hipMemcpyDeviceToHost, E.s_copy));
     HIPC(hipEventRecord(E.ev_copied[slot], E.s_copy));
     HIPC(hipEventRecord(E.ev_free[slot], E.s_copy));
     return POB_OK;
@@ -1427,7 +1440,7 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
     const uint64_t nwin_ = (E.total + window_wires - 1) / window_wires;
     // the witness announced with pob_emit_queue, same payload and window size: its first window has been expanded (and is being copied)
     // behind the previous witness' last windows already -- continue from there, nothing to wait for
-    if (E.pre_made && E.pre_made_gen == h->gen_count && E.queued_idx == (int64_t)idx && E.win_wires == window_wires && E.nwin == nwin_ && E.probe_map == E.map_id) {
+    if (E.pre_made && E.pre_made_gen == h->gen_count && E.queued_idx == (int64_t)idx && E.win_wires == window_wires && E.nwin == nwin_ && E.probe_map == E.map_id && E.pre_made_packed == E.packed) {
         E.first_slot = (E.first_slot + (uint32_t)E.nwin) % NS;
         E.idx = idx; E.next_make = 1; E.next_take = 0; E.active = true; E.queued_idx = -1; E.pre_made = false;
         return POB_OK;
@@ -1453,9 +1466,20 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
             if (E.d_win[k]) { HIPC(hipFree(E.d_win[k])); E.d_win[k] = nullptr; }
             if (E.h_pin[k]) { HIPC(hipHostFree(E.h_pin[k])); E.h_pin[k] = nullptr; }
             HIPC(hipMalloc(&E.d_win[k], window_wires * 32));
-            HIPC(hipHostMalloc((void**)&E.h_pin[k], window_wires * 32, hipHostMallocDefault));
+            HIPC(hipHostMalloc((void**)&E.h_pin[k], window_wires * 32 + pack_fixed_bytes(window_wires) + 32, hipHostMallocDefault));      // (a packed window of nothing but wide values is that much longer than the canonical one)
         }
         E.alloc_wires = window_wires;
+    }
+    if (E.packed && E.pk_alloc_wires < E.alloc_wires) {                      // the packed form of a slot and the scan's scratch: with the first packed emission at a window size
+        for (int k = 0; k < NS; k++) {
+            if (E.d_pk[k]) { HIPC(hipFree(E.d_pk[k])); E.d_pk[k] = nullptr; }
+            HIPC(hipMalloc(&E.d_pk[k], E.alloc_wires * 32 + pack_fixed_bytes(E.alloc_wires) + 32));
+        }
+        if (E.d_pk_blk) { HIPC(hipFree(E.d_pk_blk)); E.d_pk_blk = nullptr; }
+        if (E.d_pk_tot) { HIPC(hipFree(E.d_pk_tot)); E.d_pk_tot = nullptr; }
+        HIPC(hipMalloc(&E.d_pk_blk, ((E.alloc_wires + 63) / 64) * 4)); HIPC(hipMalloc(&E.d_pk_tot, ((E.alloc_wires + 4095) / 4096) * 4));
+        if (!E.s_val) HIPC(hipStreamCreateWithPriority(&E.s_val, hipStreamNonBlocking, 0));
+        E.pk_alloc_wires = E.alloc_wires;
     }
     if ((E.probe_win != window_wires || E.probe_map != E.map_id) && nwin_ <= 64) {
         // probe pass: every G unit runs once with the emitter's stores replaced by "mark window position / window_wires"; a window then
@@ -1574,11 +1598,22 @@ int pob_emit_begin(pob_handle h, uint32_t idx, uint64_t window_wires) {
     if (!h) return POB_E_ARG;
     if (!h->generated || idx >= h->n) { h->err = "nothing generated / witness index out of range"; return POB_E_STATE; }
     HIPC(hipSetDevice(h->device));
-    h->em.red = false; h->em.map_id = 0; h->em.total = h->plan.total.w;
+    h->em.red = false; h->em.map_id = 0; h->em.total = h->plan.total.w; h->em.packed = false;
     return emit_start(h, idx, window_wires);
 }
 
-int pob_emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires) {
+static int emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires, bool packed);
+int pob_emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires) { return emit_begin_reduced(h, idx, keep, n_keep, window_wires, false); }
+int pob_emit_begin_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires) {
+    if (keep) return emit_begin_reduced(h, idx, keep, n_keep, window_wires, true);
+    if (!h || n_keep) return POB_E_ARG;
+    if (!h->generated || idx >= h->n) { h->err = "nothing generated / witness index out of range"; return POB_E_STATE; }
+    HIPC(hipSetDevice(h->device));
+    h->em.red = false; h->em.map_id = 0; h->em.total = h->plan.total.w; h->em.packed = true;
+    return emit_start(h, idx, window_wires);
+}
+
+static int emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires, bool packed) {
     if (!h || !keep || n_keep == 0) return POB_E_ARG;
     if (!h->generated || idx >= h->n) { h->err = "nothing generated / witness index out of range"; return POB_E_STATE; }
     HIPC(hipSetDevice(h->device));
@@ -1610,7 +1645,7 @@ int pob_emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uin
         E.keep.assign(keep, keep + n_keep);
         E.queued_idx = -1; E.pre_made = false;
     }
-    E.red = true; E.map_id = id; E.total = n_keep;
+    E.red = true; E.map_id = id; E.total = n_keep; E.packed = packed;
     return emit_start(h, idx, window_wires);
 }
 
@@ -1622,10 +1657,11 @@ int pob_reduced_map_pin(pob_handle h, const uint32_t* keep, uint64_t n_keep) {
     return POB_OK;
 }
 
-int pob_emit_next(pob_handle h, const uint8_t** data, uint64_t* first_wire, uint64_t* n_wires) {
+static int emit_next(pob_handle h, bool packed, const uint8_t** data, uint64_t* bytes, uint64_t* first_wire, uint64_t* n_wires) {
     if (!h || !data || !first_wire || !n_wires) return POB_E_ARG;
     pob_ctx::Emit& E = h->em;
     if (!E.active) { h->err = "pob_emit_next without pob_emit_begin"; return POB_E_STATE; }
+    if (E.packed != packed) { h->err = packed ? "pob_emit_next_packed: the emission was not begun with pob_emit_begin_packed" : "pob_emit_next: the emission was begun with pob_emit_begin_packed"; return POB_E_STATE; }
     if (E.next_take == E.nwin) { E.active = false; *data = nullptr; *first_wire = E.total; *n_wires = 0; return POB_OK; }
     HIPC(hipSetDevice(h->device));
     const int NS = pob_ctx::Emit::NSLOT;
@@ -1638,13 +1674,29 @@ int pob_emit_next(pob_handle h, const uint8_t** data, uint64_t* first_wire, uint
     // ... and when this witness has no more windows to make, the first window of the witness announced with pob_emit_queue
     if (E.next_make == E.nwin && E.nwin - E.next_take <= 2 && E.queued_idx >= 0 && !E.pre_made) {
         int rc = emit_make_window(h, (uint32_t)E.queued_idx, 0, (int)((E.first_slot + E.nwin) % NS)); if (rc) return rc;
-        E.pre_made = true; E.pre_made_gen = h->gen_count;
+        E.pre_made = true; E.pre_made_gen = h->gen_count; E.pre_made_packed = E.packed;
     }
     const uint64_t k = E.next_take++;
     const int slot = (int)((E.first_slot + k) % NS);
     HIPC(hipEventSynchronize(E.ev_copied[slot]));
     *data = E.h_pin[slot]; *first_wire = k * E.win_wires; *n_wires = std::min(E.win_wires, E.total - k * E.win_wires);
+    if (packed) {             // the header is in pinned memory: its two counts give the length of the value sections, which cross now (a few MB)
+        uint32_t cnt[2]; memcpy(cnt, E.h_pin[slot] + 20, 8);
+        const uint64_t fixed = pack_fixed_bytes(*n_wires), vb = pack_value_bytes(cnt[0], cnt[1]);
+        if ((uint64_t)cnt[0] + cnt[1] > *n_wires) { h->err = "internal: packed window counts more values than wires"; return POB_E_STATE; }
+        if (vb) {
+            HIPC(hipMemcpyAsync(E.h_pin[slot] + fixed, E.d_pk[slot] + fixed, vb, hipMemcpyDeviceToHost, E.s_val));
+            HIPC(hipStreamSynchronize(E.s_val));
+            E.pk_d2h += vb;
+        }
+        if (bytes) *bytes = fixed + vb;
+    }
     return POB_OK;
+}
+int pob_emit_next(pob_handle h, const uint8_t** data, uint64_t* first_wire, uint64_t* n_wires) { return emit_next(h, false, data, nullptr, first_wire, n_wires); }
+int pob_emit_next_packed(pob_handle h, const uint8_t** data, uint64_t* bytes, uint64_t* first_wire, uint64_t* n_wires) {
+    if (!bytes) return POB_E_ARG;
+    return emit_next(h, true, data, bytes, first_wire, n_wires);
 }
 
 int pob_emit_selfcheck(pob_handle h, int enable) {
@@ -1719,13 +1771,17 @@ static int write_wtns_stream(pob_ctx* h, const char* path) {
     u32 = 32; memcpy(hdr + 24, &u32, 4); memcpy(hdr + 28, P64, 32); u32 = (uint32_t)W; memcpy(hdr + 60, &u32, 4);
     u32 = 2; memcpy(hdr + 64, &u32, 4); u64v = bytes; memcpy(hdr + 68, &u64v, 8);
     bool ok = fwrite(hdr, 1, 76, f) == 76;
+    uint8_t* canon = nullptr;                           // packed transfer: each window is expanded here on the host before it is written
+    if (h->em.packed && !(canon = (uint8_t*)malloc(h->em.win_wires * 32))) { fclose(f); remove(path); h->em.active = false; h->err = "out of host memory"; return POB_E_NOMEM; }
     for (;;) {
-        const uint8_t* p; uint64_t w0, wn;
-        int rc = pob_emit_next(h, &p, &w0, &wn);
-        if (rc) { fclose(f); remove(path); return rc; }
+        const uint8_t* p; uint64_t w0, wn, pb = 0;
+        int rc = emit_next(h, h->em.packed, &p, &pb, &w0, &wn);
+        if (!rc && wn && canon) { rc = pob_unpack_window(p, pb, canon, wn * 32, 0); if (rc) h->err = "internal: a packed window does not validate"; p = canon; }
+        if (rc) { fclose(f); remove(path); free(canon); return rc; }
         if (!wn) break;
         if (ok) ok = fwrite(p, 1, wn * 32, f) == wn * 32;
     }
+    free(canon);
     fclose(f);
     if (!ok) { remove(path); h->err = "write failed"; return POB_E_IO; }
     return POB_OK;
@@ -1738,6 +1794,11 @@ int pob_write_wtns(pob_handle h, uint32_t idx, const char* path) {
 int pob_write_wtns_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, const char* path) {
     if (!h || !path) return POB_E_ARG;
     int rc = pob_emit_begin_reduced(h, idx, keep, n_keep, 0);
+    return rc ? rc : write_wtns_stream(h, path);
+}
+int pob_write_wtns_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, const char* path) {
+    if (!h || !path) return POB_E_ARG;
+    int rc = pob_emit_begin_packed(h, idx, keep, n_keep, 0);
     return rc ? rc : write_wtns_stream(h, path);
 }
 
@@ -1763,6 +1824,36 @@ int pob_emit_measure_ex(pob_handle h, uint32_t first_idx, uint32_t count, uint64
     }
     clock_gettime(CLOCK_MONOTONIC, &t1);
     *seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec); *bytes = total;
+    return POB_OK;
+}
+// the packed form: pass 1 takes the packed windows as they arrive in pinned memory, pass 2 also expands each into dst (the whole payload if it fits dst_cap, else every
+// window at dst's start); d2h_bytes = what pass 1 copied device-to-host
+int pob_emit_measure_packed(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
+                            double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes) {
+    if (!h || !seconds_pinned || !d2h_bytes || count == 0 || threads < 0 || (dst && !seconds_expanded)) return POB_E_ARG;
+    HIPC(hipSetDevice(h->device));
+    for (int pass = 0; pass < (dst ? 2 : 1); pass++) {
+        const uint64_t d0 = h->em.pk_d2h; volatile uint8_t sink = 0;
+        timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+        for (uint32_t i = 0; i < count; i++) {
+            int rc = pob_emit_begin_packed(h, first_idx + i, keep, n_keep, window_wires);
+            if (rc) return rc;
+            const bool whole = dst_cap >= h->em.total * 32;
+            if (pass && !whole && dst_cap < h->em.win_wires * 32) { h->em.active = false; h->err = "destination smaller than a window"; return POB_E_ARG; }
+            if (i + 1 < count) { rc = pob_emit_queue(h, first_idx + i + 1); if (rc) return rc; }
+            for (;;) {
+                const uint8_t* p; uint64_t pb, w0, wn;
+                rc = pob_emit_next_packed(h, &p, &pb, &w0, &wn);
+                if (rc) return rc;
+                if (!wn) break;
+                sink = sink ^ p[0] ^ p[pb - 1];
+                if (pass) { rc = pob_unpack_window(p, pb, whole ? dst + w0 * 32 : dst, wn * 32, threads); if (rc) { h->em.active = false; h->err = "internal: a packed window does not validate"; return rc; } }
+            }
+        }
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const double sec = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+        if (pass) *seconds_expanded = sec; else { *seconds_pinned = sec; *d2h_bytes = h->em.pk_d2h - d0; }
+    }
     return POB_OK;
 }
 int pob_emit_measure(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t window_wires, double* seconds, uint64_t* bytes) {

@@ -181,6 +181,13 @@ def load_library() -> ctypes.CDLL:
     lib.pob_emit_next.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.pob_emit_queue.argtypes = [vp, ctypes.c_uint32]
     lib.pob_emit_measure.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(lib, "pob_emit_begin_packed"):      # (absent only in an older build named by POB_LIB_PATH, measured beside this one: tools/emit_rate.py --parent; build() checks every export)
+        lib.pob_emit_begin_packed.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_uint64]
+        lib.pob_emit_next_packed.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        lib.pob_unpack_window.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int]
+        lib.pob_write_wtns_packed.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_char_p]
+        lib.pob_emit_measure_packed.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
     lib.pob_time_kernel.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
     lib.pob_probe_check_kernel.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     lib.pob_debug_xor_bits.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
@@ -208,7 +215,7 @@ EXPORTED_SYMBOLS = ["pob_plan_info", "pob_gadget_template", "pob_open", "pob_clo
                     "pob_upload_inputs8", "pob_upload_inputs8_async", "pob_narrow_inputs", "pob_pack_json_batch8",
                     "pob_results_fetch", "pob_results_wait", "pob_emit_begin_reduced", "pob_reduced_map_pin", "pob_write_wtns_reduced", "pob_emit_measure_ex", "pob_generate",
                     "pob_constraint_check", "pob_sync", "pob_set_partner", "pob_results", "pob_results_device", "pob_results_records_device", "pob_gather_records", "pob_emit_witness",
-                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
+                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
 
 
 def plan_info(main: str) -> PobInfo:
@@ -808,6 +815,48 @@ class WitnessCalculator:
                                               ctypes.byref(sec), ctypes.byref(nb)))
         return sec.value, nb.value
 
+    # ---- packed windows (pob_emit_begin_packed: 2-bit tags + the values that are neither 0 nor 1; format in include/pob_hip.h and INTEGRATION.md)
+    def packed_windows(self, idx: int = 0, window_wires: int = 0, keep=None):
+        """stream witness idx as packed windows: yields (first_wire, n_wires, uint8 view of the packed window) per window; a view is valid until the next
+        iteration (it aliases the handle's pinned buffer).  keep: the reduced payload (positions count kept wires)"""
+        k = None if keep is None else self._keep_array(keep)
+        self._ck(self.lib.pob_emit_begin_packed(self.h, idx, k.ctypes.data if k is not None else None, k.size if k is not None else 0, window_wires))
+        p, nb, w0, wn = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        while True:
+            self._ck(self.lib.pob_emit_next_packed(self.h, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(w0), ctypes.byref(wn)))
+            if wn.value == 0:
+                return
+            buf = (ctypes.c_uint8 * nb.value).from_address(p.value)
+            yield w0.value, wn.value, np.frombuffer(buf, dtype=np.uint8)
+
+    def unpack_window(self, buf, out: np.ndarray | None = None, threads: int = 0) -> np.ndarray:
+        return unpack_window(buf, out, threads)
+
+    def witness_payload_packed(self, idx: int = 0, keep=None, window_wires: int = 0) -> np.ndarray:
+        """the canonical payload (O0, or reduced at `keep`) as one array, through the packed transfer and the native host expansion"""
+        k = None if keep is None else self._keep_array(keep)
+        out = np.empty(32 * (self.nwitness if k is None else k.size), dtype=np.uint8)
+        for w0, wn, view in self.packed_windows(idx, window_wires, keep=k):
+            unpack_window(view, out[32 * w0:32 * (w0 + wn)])
+        return out
+
+    def write_wtns_packed(self, idx: int, path: str, keep=None):
+        """the .wtns file of write_wtns (keep=None) / write_wtns_reduced, byte for byte, through the packed transfer (pob_write_wtns_packed)"""
+        k = None if keep is None else self._keep_array(keep)
+        self._ck(self.lib.pob_write_wtns_packed(self.h, idx, k.ctypes.data if k is not None else None, k.size if k is not None else 0, os.fsencode(path)))
+
+    def emit_throughput_packed(self, first_idx: int = 0, count: int = 1, window_wires: int = 0, keep=None, out: np.ndarray | None = None, threads: int = 0):
+        """(seconds until the packed windows of `count` witnesses are in pinned memory, seconds with the host expansion into `out` included -- None without `out` --, bytes
+        copied device-to-host).  out: uint8, the whole payload or at least one window (pob_emit_measure_packed)"""
+        s0, s1, nb = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
+        k = None if keep is None else self._keep_array(keep)
+        if out is not None and (out.dtype != np.uint8 or not out.flags.c_contiguous):
+            raise ValueError("out: a contiguous uint8 array")
+        self._ck(self.lib.pob_emit_measure_packed(self.h, first_idx, count, window_wires, k.ctypes.data if k is not None else None, k.size if k is not None else 0,
+                                                  out.ctypes.data if out is not None else None, out.nbytes if out is not None else 0, threads,
+                                                  ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(nb)))
+        return s0.value, (s1.value if out is not None else None), nb.value
+
     def time_kernel(self, which: int, iters: int = 5, stream: int | None = None) -> float:
         ms = ctypes.c_float()
         self._ck(self.lib.pob_time_kernel(self.h, which, iters, ctypes.c_void_p(stream) if stream else None, ctypes.byref(ms)))
@@ -932,6 +981,21 @@ class PinnedInputs:
         for p in self._p:
             self.lib.pob_host_free(p)
         self._p = []
+
+
+def unpack_window(buf, out: np.ndarray | None = None, threads: int = 0) -> np.ndarray:
+    """one packed window (bytes-like / uint8 array) -> its canonical 32-byte values (pob_unpack_window: host only, no GPU touched; threads = 0: the loader pool's width).
+    out: a contiguous uint8 buffer to fill (its size is the capacity the library may use).  ValueError for a window that does not validate or does not fit."""
+    b = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, dtype=np.uint8)
+    n = int.from_bytes(b[16:20].tobytes(), "little") if b.size >= 32 else 0
+    if out is None:
+        out = np.empty(32 * n, dtype=np.uint8)
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError("out: a contiguous uint8 array")
+    rc = load_library().pob_unpack_window(b.ctypes.data, b.size, out.ctypes.data, out.size, threads)
+    if rc != 0:
+        raise ValueError(f"pob_unpack_window: not a valid packed window, or the destination is smaller than 32 bytes per wire (code {rc})")
+    return out[:32 * n]
 
 
 def wtns_header(nwitness: int) -> bytes:

@@ -1,24 +1,159 @@
 #!/usr/bin/env python3
-"""Emission rates of ONE production calculator: the O0 payload and the reduced (O1-style) one, steady state (POB_LIB_PATH selects the build)."""
+"""Emission rates of ONE production calculator: the O0 payload and the reduced (O1-style) one, steady state (POB_LIB_PATH selects the build).
+    python tools/emit_rate.py [label]                    the canonical paths (pob_emit_measure_ex)
+    python tools/emit_rate.py --packed [--pairs N] [--parent LIB]
+        the packed transfer (pob_emit_measure_packed) beside the canonical one.  --parent: another build of the library (the parent commit's) measured in a second
+        process that takes turns with this one, pair by pair, on the same GPU: its canonical figures are the baseline.  Prints medians and ranges.
+    python tools/emit_rate.py --trace-one                ONE packed O0 production emission and nothing else after the generation (for rocprofv3 --kernel-trace --stats)"""
+import json
 import os
+import statistics
+import subprocess
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from proof_of_burn_amd import WitnessCalculator, inputs as gen  # noqa: E402
-from proof_of_burn_amd.circuit_model import keepmap  # noqa: E402
 
 MAIN = "ProofOfBurn(16, 4, 16, 50, 31, 2, 10 ** 19, 10 ** 20)"
-batch = gen.synthetic_batch(64, depth=10, seed=0xB0B, distinct_keys=4)
-calc = WitnessCalculator(MAIN, max_batch=64)
-res = calc.calculate(batch.inputs, check=True)
-assert all(r.ok for r in res)
-calc.emit_throughput(0, count=1)
-sec, nbytes = calc.emit_throughput(1, count=3)
-keep, _ = keepmap.load(MAIN)
-calc.emit_throughput(0, count=1, keep=keep, window_wires=1 << 24)
-out = []
-for rep in range(3):
-    rsec, rbytes = calc.emit_throughput(1, count=6, keep=keep, window_wires=1 << 24)
-    out.append(round(rsec / 6 * 1e3, 2))
-print(f"{sys.argv[1] if len(sys.argv) > 1 else 'lib'}: O0 payload {nbytes / sec / 1e9:.1f} GB/s ({sec / 3 * 1e3:.1f} ms per witness); reduced {out} ms per witness")
-calc.close()
+RED_WIN = 1 << 24
+
+
+def open_calc():
+    from proof_of_burn_amd import WitnessCalculator, inputs as gen
+    from proof_of_burn_amd.circuit_model import keepmap
+    batch = gen.synthetic_batch(64, depth=10, seed=0xB0B, distinct_keys=4)
+    calc = WitnessCalculator(MAIN, max_batch=64)
+    res = calc.calculate(batch.inputs, check=True)
+    assert all(r.ok for r in res)
+    keep, _ = keepmap.load(MAIN)
+    return calc, keep
+
+
+def legacy(label):
+    calc, keep = open_calc()
+    calc.emit_throughput(0, count=1)
+    sec, nbytes = calc.emit_throughput(1, count=3)
+    calc.emit_throughput(0, count=1, keep=keep, window_wires=RED_WIN)
+    out = []
+    for rep in range(3):
+        rsec, rbytes = calc.emit_throughput(1, count=6, keep=keep, window_wires=RED_WIN)
+        out.append(round(rsec / 6 * 1e3, 2))
+    print(f"{label}: O0 payload {nbytes / sec / 1e9:.1f} GB/s ({sec / 3 * 1e3:.1f} ms per witness); reduced {out} ms per witness")
+    calc.close()
+
+
+def serve():
+    """a measuring process driven over stdin / stdout: 'canon' / 'packed' / 'unpack' -> one JSON line each; every kind is warmed up before its first measurement
+    (the first emission of a handle at a window size allocates the window buffers and probes)"""
+    import numpy as np
+    calc, keep = open_calc()
+    warm, buf = set(), None
+    print(json.dumps({"ready": True}), flush=True)
+    for line in sys.stdin:
+        cmd = line.strip()
+        if cmd == "quit":
+            break
+        if cmd == "canon":
+            if cmd not in warm:
+                calc.emit_throughput(0, count=1); calc.emit_throughput(0, count=1, keep=keep, window_wires=RED_WIN); warm.add(cmd)
+            s0, b0 = calc.emit_throughput(1, count=3)
+            s1, b1 = calc.emit_throughput(1, count=6, keep=keep, window_wires=RED_WIN)
+            print(json.dumps({"o0_ms": s0 / 3 * 1e3, "o0_bytes": b0 // 3, "red_ms": s1 / 6 * 1e3, "red_bytes": b1 // 6}), flush=True)
+        elif cmd == "packed":
+            if buf is None:
+                buf = np.zeros(32 * RED_WIN, dtype=np.uint8)              # one window of either kind (O0: 8 Mi wires, reduced: 16 Mi): every window is expanded to its start
+            if cmd not in warm:
+                calc.emit_throughput_packed(0, 1, 0, out=buf); calc.emit_throughput_packed(0, 1, RED_WIN, keep=keep, out=buf); warm.add(cmd)
+            p0, e0, d0 = calc.emit_throughput_packed(1, 3, 0, out=buf)
+            p1, e1, d1 = calc.emit_throughput_packed(1, 6, RED_WIN, keep=keep, out=buf)
+            print(json.dumps({"o0_pinned_ms": p0 / 3 * 1e3, "o0_expanded_ms": e0 / 3 * 1e3, "o0_d2h": d0 // 3,
+                              "red_pinned_ms": p1 / 6 * 1e3, "red_expanded_ms": e1 / 6 * 1e3, "red_d2h": d1 // 6}), flush=True)
+        elif cmd == "unpack":
+            from proof_of_burn_amd import witness as W
+            if buf is None:
+                buf = np.zeros(32 * RED_WIN, dtype=np.uint8)
+            out = {}
+            for name, kp, win in (("o0", None, 0), ("red", keep, RED_WIN)):
+                wins = [(wn, v.copy()) for _, wn, v in calc.packed_windows(1, win, keep=kp)][:2]      # the first window holds most values that are not bits, the second is typical
+                for k, (wn, pk) in enumerate(wins):
+                    W.unpack_window(pk, buf)
+                    ts = []
+                    for _ in range(5):
+                        t0 = time.perf_counter(); W.unpack_window(pk, buf); ts.append(time.perf_counter() - t0)
+                    out[f"{name}_window{k}"] = {"wires": wn, "packed_bytes": int(pk.size), "ms": statistics.median(ts) * 1e3, "canonical_GBps": 32 * wn / statistics.median(ts) / 1e9}
+            print(json.dumps(out), flush=True)
+    calc.close()
+
+
+class Proc:
+    def __init__(self, lib=None):
+        env = dict(os.environ)
+        if lib:
+            env["POB_LIB_PATH"] = os.path.abspath(lib)
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--serve"], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env)
+        assert json.loads(self.p.stdout.readline())["ready"]
+
+    def ask(self, cmd):
+        self.p.stdin.write(cmd + "\n"); self.p.stdin.flush()
+        line = self.p.stdout.readline()
+        if not line:
+            raise RuntimeError(f"the measuring process ended (exit {self.p.wait()})")
+        return json.loads(line)
+
+    def close(self):
+        self.p.stdin.write("quit\n"); self.p.stdin.flush(); self.p.wait(120)
+
+
+def _fmt(xs, unit="ms"):
+    return f"median {statistics.median(xs):.2f} {unit} (range {min(xs):.2f} .. {max(xs):.2f}, n = {len(xs)})"
+
+
+def packed(pairs, parent):
+    new = Proc()
+    old = Proc(parent) if parent else None
+    rows = {"new_canon": [], "new_packed": [], "parent_canon": []}
+    try:
+        for who in (old, new):                                        # warm-up emissions of every kind, each library
+            if who is not None:
+                who.ask("canon")
+        new.ask("packed")
+        for _ in range(pairs):                                        # parent and new library take turns
+            if old is not None:
+                rows["parent_canon"].append(old.ask("canon"))
+            rows["new_canon"].append(new.ask("canon"))
+            rows["new_packed"].append(new.ask("packed"))
+        unpack = new.ask("unpack")
+    finally:
+        for who in (old, new):
+            if who is not None:
+                who.close()
+    print(f"{MAIN}, one calculator, 64 witnesses resident; per witness, steady state; {pairs} rounds, the libraries taking turns on one GPU")
+    for form, key in (("O0 (215 907 954 wires, windows of 8 Mi)", "o0"), ("reduced (21 454 032 kept wires, windows of 16 Mi)", "red")):
+        print(f"{form}:")
+        if old is not None:
+            print(f"  parent library, canonical into pinned memory:   {_fmt([r[key + '_ms'] for r in rows['parent_canon']])}, {rows['parent_canon'][0][key + '_bytes']} B D2H")
+        print(f"  this library,   canonical into pinned memory:   {_fmt([r[key + '_ms'] for r in rows['new_canon']])}, {rows['new_canon'][0][key + '_bytes']} B D2H")
+        print(f"  this library,   packed into pinned memory:      {_fmt([r[key + '_pinned_ms'] for r in rows['new_packed']])}, {rows['new_packed'][0][key + '_d2h']} B D2H")
+        print(f"  this library,   packed + host expansion:        {_fmt([r[key + '_expanded_ms'] for r in rows['new_packed']])} (pob_unpack_window on the pool's default width, every window into one buffer)")
+    print("host expansion alone (pob_unpack_window, pool's default width, median of 5):")
+    for k, v in unpack.items():
+        print(f"  {k}: {v['wires']} wires, {v['packed_bytes']} B packed -> {v['ms']:.2f} ms, {v['canonical_GBps']:.1f} GB/s of canonical bytes written")
+
+
+def trace_one():
+    calc, _ = open_calc()
+    sec, _, d2h = calc.emit_throughput_packed(1, 1, 0)
+    print(f"one packed O0 emission (first of the handle: allocation and probe pass included): {sec * 1e3:.1f} ms, {d2h} B D2H")
+    calc.close()
+
+
+if __name__ == "__main__":
+    a = sys.argv[1:]
+    if "--serve" in a:
+        serve()
+    elif "--trace-one" in a:
+        trace_one()
+    elif "--packed" in a:
+        packed(int(a[a.index("--pairs") + 1]) if "--pairs" in a else 5, a[a.index("--parent") + 1] if "--parent" in a else None)
+    else:
+        legacy(a[0] if a else "lib")
