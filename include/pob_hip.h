@@ -36,11 +36,16 @@ typedef struct {
                                     sums (Selector.sum[], SubstringCheck.M[]); round 4: BIT-valued copies of stored bits (the padded bytes' bits, the
                                     hash bits, the Keccak output selectors' vals[] / isEq[] / sum[] and their children, AssertByteString's bits) and the
                                     products of ShiftRight / ShiftLeft / CompConstant.  Generation and evaluation skip them; the emitter rebuilds them from
-                                    the same expressions; pob_emit_selfcheck evaluates their relations on the values it writes                         */
-    uint64_t n_alias;            /* wires of the Keccak round blocks that are not stored because they ARE another wire: copies of a stored gate
+                                    the same expressions; pob_emit_selfcheck evaluates their relations on the values it writes.  Keccak.in / Final.in
+                                    (copies of KeccakBytes.inBlocks) and Final.s (zero, then every Absorb block's output) are counted here too          */
+    uint64_t n_alias;            /* wires of the Absorb blocks that are not stored because they ARE another wire.  Round blocks: copies of a stored gate
                                     output / of the round's input or output state, possibly at a rotated bit position (ShL / ShR / RhoPi) or negated
-                                    (NotArray), or constants (shifted-out positions, round constants).  76 of the 1 604 arrays of a KeccakfRound
-                                    block are stored (keccak_kernels.hpp); the emitter expands the others through one table                          */
+                                    (NotArray), or constants (shifted-out positions, round constants); 76 of the 1 604 arrays of a KeccakfRound
+                                    block are stored (keccak_kernels.hpp), the emitter expands the others through one table.  Sponge chain (the wires of
+                                    an Absorb block ahead of its round blocks): only Keccakf's midRound[0..24] are stored -- the XorArray outputs and the
+                                    rounds' outputs; Absorb.out / s / block / aux, the XorArrays' out / a / b and (o, a, b) triples and Keccakf.in / out
+                                    are copies of those words, of the previous block's midRound[24] (zero for block 0) or of KeccakBytes.inBlocks: their
+                                    copy constraints hold by construction, the emitter expands them (keccak_kernels.hpp absorb_wire_word)               */
     uint32_t kchk_rounds;        /* consecutive rounds of a permutation that ONE wavefront of the round evaluation covers (k_rounds_check): it fetches
                                     midRound[r0] once and then 101 arrays per round, the verified midRound[r+1] staying in registers as the next round's
                                     input -- (101 k + 25) / k arrays of 512 B per (64 witnesses, round)                                               */
@@ -323,7 +328,7 @@ int pob_debug_fr_inv(int device, const uint8_t* in, uint32_t n, uint8_t* out_kal
 int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr, uint8_t* out_mul);
 /* Test hook: storage class, rank within the class and wire index of a few named wires: "commitment"; "poseidon" (k-th wire of the
  * first Poseidon block), "poseidon.t3" / ".t4" / ".t5" (... of the first Poseidon block of width T = 3 / 4 / 5); "pad.div.out" / "pad.div.rem" of KeccakBytes instance k (the Divide hint of divide.circom:23-24); ProofOfBurn only: "sc.exists" [k] of layer 1's SubstringCheck. */
-int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k */
+int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k; "kb.inBlocks": its first inBlocks bit; "kb.absorb": the first stored word (midRound[0][0][0]) and the first wire of its first Absorb block */
 
 /* Host helper used by the input producers (next row f1): Keccak-256 of a byte string.                           */
 void pob_keccak256(const uint8_t* msg, uint64_t len, uint8_t out[32]);

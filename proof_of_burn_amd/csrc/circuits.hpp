@@ -19,17 +19,22 @@
 #define KECCAKF_WIRES (43200u + 24u * KECCAKF_ROUND_WIRES)        // 2 506 944
 #define ABSORB_OWN 5888u                                            // out, s, block[17], aux
 #define ABSORB_WIRES (ABSORB_OWN + 17u * 384u + KECCAKF_WIRES)     // 2 519 360
-// Storage of an Absorb block (round 4).  Its own wires, its 17 XorArrays and Keccakf's own wires (out, in, midRound[25]) are stored 1:1
-// (AB_DIRECT BIT ranks in wire order).  Of the 102 656 wires of a KeccakfRound block only the KR_STORED = 76 arrays of 64 that are OUTPUTS
-// OF A GATE and not the round's output state are stored (20 Xor5 partials, 5 D, 25 theta, 25 chi-AND, chi.out[0] before iota); every other
-// wire of the block is an ALIAS: a copy of a stored wire / of midRound[r] / of midRound[r+1], possibly at a rotated bit position or
-// negated (NotArray), or a constant (shifted-out positions, round constants).  keccak_kernels.hpp states which (one walker), the emitter
-// expands through that table.
+// Storage of an Absorb block: GATE OUTPUTS only.  Ahead of the round blocks (wire offsets below AB_ROUNDS_W) the only gate outputs are Keccakf's
+// midRound[0..24] -- midRound[0] is the 17 XorArray outputs and s[17..24], midRound[r + 1] the output of round r -- stored as AB_DIRECT BIT ranks from
+// the block's first rank (AB_MID) on.  Every other wire there (Absorb.out / s / block / aux, the XorArrays' out / a / b and their 64 (o, a, b) triples,
+// Keccakf.in / out) is an ALIAS: a copy of a midRound[0] / midRound[24] word, of the previous block's midRound[24] (zero for block 0) or of
+// KeccakBytes.inBlocks (keccak_kernels.hpp absorb_wire_word states which).  Of the 102 656 wires of a KeccakfRound block only the KR_STORED = 76
+// arrays of 64 that are OUTPUTS OF A GATE and not the round's output state are stored (20 Xor5 partials, 5 D, 25 theta, 25 chi-AND, chi.out[0] before
+// iota); every other wire of the block is an alias too: a copy of a stored wire / of midRound[r] / of midRound[r+1], possibly at a rotated bit
+// position or negated (NotArray), or a constant (shifted-out positions, round constants).  keccak_kernels.hpp states which (one walker), the emitter
+// expands through that table.  (Round 4 stored all AB_ROUNDS_W wires ahead of the round blocks 1:1: 928 arrays per permutation of which 303 copies.)
 #define KR_STORED 76u
 #define KR_BITS (KR_STORED * 64u)                                   // 4 864 BIT ranks per round block
-#define AB_DIRECT (ABSORB_OWN + 17u * 384u + 43200u)               // 55 616
-#define ABSORB_BITS (AB_DIRECT + 24u * KR_BITS)                    // 172 352
-#define ABSORB_ALIAS (ABSORB_WIRES - ABSORB_BITS)                  // 2 347 008 alias wires per permutation
+#define AB_ROUNDS_W (ABSORB_OWN + 17u * 384u + 43200u)             // 55 616: wire offset of KeccakfRound(0) in the Absorb block
+#define AB_MID 0u                                                   // BIT rank of midRound[0][0] relative to the block's first
+#define AB_DIRECT (25u * 1600u)                                     // 40 000 BIT ranks ahead of the round blocks' (midRound[0..24])
+#define ABSORB_BITS (AB_DIRECT + 24u * KR_BITS)                    // 156 736
+#define ABSORB_ALIAS (ABSORB_WIRES - ABSORB_BITS)                  // 2 362 624 alias wires per permutation
 
 enum UnitKind : uint32_t {
     U_POB_INPUT = 1, U_POB_RANGE, U_POB_LAYER_ASSERT, U_POB_HDR_ASSERT, U_POB_POSEIDONS, U_BAH_PRE, U_BAH_POST,
@@ -148,7 +153,7 @@ struct RaRefs {
     SmRef ri_o, ri_ol; FrRef ri_i; SmRef by, len, be; BitRef isb, isz; SmRef frb;             // RlpInteger own
     Cur c_cb, c_sl, c_lt, c_concat, c_end;
 };
-struct SpongeDesc { uint32_t n, stage, src_b, kin_b, fin_b, fs_b, abs_b, kin_w, fin_w, fs_w, abs_w, src_w; };
+struct SpongeDesc { uint32_t n, stage, src_b, abs_b, kin_w, fin_w, fs_w, abs_w, src_w; };      // (Keccak.in / Final.in / Final.s: wire indices only -- copies of inBlocks / of the blocks' midRound[24])
 struct UnitDesc { uint32_t kind, stage; Cur cur; uint32_t a[8]; uint32_t cost, flags; };
 
 #define SC_RANGE_POS 32          // positions of SubstringCheck's existence loop per unit (one batch inversion each; <= 64: the zero flags are one 64-bit word).  64 measured: generation 1.07 -> 1.00 ms alone, evaluation 0.40 -> 0.57 ms
@@ -307,8 +312,9 @@ template <class P> GD void kb_range(P& p, const KBRefs& r, SmRef src, uint32_t l
 // Keccak(n) :374-385 / Final(n) :330-349 own wires + the n Absorb blocks (K kernels) + SelectorArray2D own wires.
 template <class P> GD void kb_declare_keccak(P& p, KBRefs& r) {
     const uint32_t n = r.mb;
-    r.k_out = dbits(p, 256); r.k_in = p.bits(n * 1088); r.k_blocks = p.sms(1); r.k_finalState = dbits(p, 1600);
-    r.f_out = dbits(p, 1600); r.f_in = p.bits(n * 1088); r.f_blocks = p.sms(1); r.f_s = p.bits((n + 1) * 1600);
+    // (Keccak.in / Final.in: copies of KeccakBytes.inBlocks; Final.s[0] = 0, Final.s[k + 1] = Absorb k's output = its midRound[24]: derived, expanded by the emitter from those words)
+    r.k_out = dbits(p, 256); r.k_in = dbits(p, n * 1088); r.k_blocks = p.sms(1); r.k_finalState = dbits(p, 1600);
+    r.f_out = dbits(p, 1600); r.f_in = dbits(p, n * 1088); r.f_blocks = p.sms(1); r.f_s = dbits(p, (n + 1) * 1600);
     r.abs_w = p.cur.w; r.abs_b = p.cur.b;
     p.skip_alias(n * ABSORB_WIRES, n * ABSORB_BITS);
     r.sel_out = dbits(p, 1600); r.sel_arrays = dbits(p, (n + 1) * 1600); r.sel_select = p.sms(1); r.sel_T = dbits(p, 1600 * (n + 1));      // (copies of Selector.out / of Final.s: derived)
@@ -335,7 +341,7 @@ template <class P, int N1> GD void kb_selrow_n(P& p, const KBRefs& r, uint32_t r
     p.run_derived(n, bw + 2 * n1 + 2, 0);                                   // sum[0]
 #pragma unroll
     for (uint32_t k = 0; k < n1; k++) {
-        const B v = p.run_get(n, r.f_s.i + k * 1600 + idx);
+        const B v = k == 0 ? (B)0 : p.run_get(n, r.abs_b + (k - 1) * ABSORB_BITS + AB_MID + 24u * 1600u + idx);      // Final.s[k]: zero | Absorb k-1's midRound[24] (the stored word)
         const B e = p.ballot((uint32_t)blocks == k);
         acc |= e & v;
         if constexpr (P::is_emit) {
@@ -1148,7 +1154,7 @@ struct Plan {
         r.index = kb;
         kb_declare_keccak(p, r);
         SpongeDesc s; s.n = r.mb; s.stage = range_stage + 1; s.src_b = r.inBlocks.i; s.src_w = r.inBlocks.w;
-        s.kin_b = r.k_in.i; s.kin_w = r.k_in.w; s.fin_b = r.f_in.i; s.fin_w = r.f_in.w; s.fs_b = r.f_s.i; s.fs_w = r.f_s.w; s.abs_b = r.abs_b; s.abs_w = r.abs_w;
+        s.kin_w = r.k_in.w; s.fin_w = r.f_in.w; s.fs_w = r.f_s.w; s.abs_b = r.abs_b; s.abs_w = r.abs_w;
         sponges.push_back(s);
         r.dst = dst; r.has_dst = has_dst ? 1 : 0;
         {   // Reshape/Bits2Num blocks start after the 1600 selectors (all of equal footprint)

@@ -324,7 +324,11 @@ static inline bool keccak_round_alias_table(uint16_t* tab) {
 
 
 // Sponge chain (Final/Absorb, keccak.circom:304-349): everything of Keccak(n)/Final(n)/Absorb x n EXCEPT the 24 round
-// blocks and the output selector: Keccak.in, Final.in, Final.s[0..n], Absorb own wires + 17 XorArrays, Keccakf in/out/midRound.
+// blocks and the output selector.  What it STORES are the gate outputs among those wires: per block Keccakf's midRound[0] (the 17 XorArray
+// outputs s[i] ^ block[i], then s[17..24]) and the 24 round outputs midRound[1..24].  Keccak.in, Final.in, Final.s, Absorb's own wires, the XorArrays'
+// operand wires and (o, a, b) triples and Keccakf's in / out are copies of those words, of the previous block's midRound[24] or of KeccakBytes.inBlocks:
+// alias wires (circuits.hpp AB_DIRECT) that only the emitter expands (absorb_wire_word), their copy constraints hold by construction.  (Rounds 4-6 stored
+// all 928 arrays per permutation 1:1 in wire order, the triples at a 24-byte lane stride: 303 arrays of copies, 208 MB per 1 024 production witnesses.)
 // (<= 128 VGPRs: the small sponges of a side track must fit the slot a k_rounds wave frees, see g_gen_heavy_small.hip)
 // (every kernel of this file is a BODY -- a device function of the launch arguments and the (item, group) of its wavefront -- plus a __global__ wrapper, so that a launch
 //  can carry the wavefronts of several independent kernels: fused launches, g_*.hip)
@@ -338,38 +342,20 @@ __device__ __forceinline__ void chain_body(const KArgs A, uint32_t bx, uint32_t 
     u64 st[25];
 #pragma unroll
     for (int i = 0; i < 25; i++) st[i] = 0;
-    auto put = [&](uint32_t idx, u64 v) { G[idx + lane] = v; };
     for (uint32_t b = 0; b < sp.n; b++) {
-        const uint32_t Ab = sp.abs_b + b * ABSORB_BITS;
-        u64 blk[17], aux[25];
+        u64* mid = G + sp.abs_b + b * ABSORB_BITS + AB_MID + lane;
+        const u64* blk = G + sp.src_b + b * 1088 + lane;
 #pragma unroll
-        for (int i = 0; i < 17; i++) blk[i] = G[sp.src_b + b * 1088 + 64 * i + lane];
+        for (int i = 0; i < 17; i++) st[i] ^= blk[64 * i];
 #pragma unroll
-        for (int i = 0; i < 25; i++) { put(sp.fs_b + b * 1600 + 64 * i, st[i]); put(Ab + 1600 + 64 * i, st[i]); }
-#pragma unroll
-        for (int i = 0; i < 17; i++) {
-            put(sp.kin_b + b * 1088 + 64 * i, blk[i]); put(sp.fin_b + b * 1088 + 64 * i, blk[i]); put(Ab + 3200 + 64 * i, blk[i]);
-            const u64 o = st[i] ^ blk[i];
-            const uint32_t X = Ab + ABSORB_OWN + 384 * i;
-            put(X, o); put(X + 64, st[i]); put(X + 128, blk[i]);
-            { u64* q = G + X + 192 + 3 * lane; q[0] = o; q[1] = st[i]; q[2] = blk[i]; }
-            aux[i] = o;
-        }
-#pragma unroll
-        for (int i = 17; i < 25; i++) aux[i] = st[i];
-        const uint32_t Kf = Ab + AB_KECCAKF;
-#pragma unroll
-        for (int i = 0; i < 25; i++) { put(Ab + 4288 + 64 * i, aux[i]); put(Kf + 1600 + 64 * i, aux[i]); put(Kf + KF_MID + 64 * i, aux[i]); st[i] = aux[i]; }
+        for (int i = 0; i < 25; i++) mid[64 * i] = st[i];
         for (int r = 0; r < 24; r++) {
             round_native(st, r, lane);
+            mid += 1600;
 #pragma unroll
-            for (int i = 0; i < 25; i++) put(Kf + KF_MID + 1600 * (r + 1) + 64 * i, st[i]);
+            for (int i = 0; i < 25; i++) mid[64 * i] = st[i];
         }
-#pragma unroll
-        for (int i = 0; i < 25; i++) { put(Kf + 64 * i, st[i]); put(Ab + 64 * i, st[i]); }
     }
-#pragma unroll
-    for (int i = 0; i < 25; i++) put(sp.fs_b + sp.n * 1600 + 64 * i, st[i]);
 }
 #ifdef POB_KECCAK_TU          // (the non-template kernels are defined in ONE translation unit, k_keccak.hip; the bodies and the template kernels wherever they are used)
 __global__ void __launch_bounds__(64, 3) k_chain(KArgs A) { chain_body(A, blockIdx.x, blockIdx.y); }
@@ -378,35 +364,32 @@ __global__ void __launch_bounds__(64, 3) k_chain(KArgs A) { chain_body(A, blockI
 // (round 5 tried TWO wavefronts per (group, sponge), each on the 32-bit half of every word -- 32-bit logic, one ds_bpermute per rotation: the header's 17-block chain
 //  0.433 -> 0.336 ms alone, but the step went from 1.57-1.60 / 1.39 to 1.67 / 1.52-1.53 ms with 4 / 8 in flight: twice the wavefronts storing 4-byte halves of every
 //  8-byte word is twice the store transactions on a write path the round expansion already saturates; profiles/round5_experiments.txt 8.  Not kept.)
-// Constraint evaluation of the same wires, LOCAL per permutation (every relation of Absorb/Final/Keccakf's own wires is
-// between stored wires, so no permutation needs to be recomputed): grid.x = (sponge, block), grid.y = group.
+// Constraint evaluation of the chain, LOCAL per permutation: the relations that are left BETWEEN STORED WORDS -- midRound[0][i] == s[i] ^ inBlocks[i] for i < 17,
+// midRound[0][i] == s[i] above, s = the previous block's stored midRound[24], zero for block 0 (:337-341) -- so no permutation needs to be recomputed:
+// grid.x = (sponge, block), grid.y = group.  67 arrays per permutation (the 1:1 layout's evaluation loaded 395, nearly all of them copies against their source).
 __device__ __forceinline__ void chain_check_body(const KArgs A, uint32_t bx, uint32_t by) {
     const uint32_t lane = threadIdx.x;
     const uint32_t pi = A.first + bx;
     const SpongeDesc sp = A.sponges[A.perm_sponge[pi]];
     const uint32_t b = A.perm_block[pi];
     const u64* G = A.bits + (uint64_t)by * A.group_stride;
-    const uint32_t Ab = sp.abs_b + b * ABSORB_BITS, Kf = Ab + AB_KECCAKF;
+    const u64* mid = G + sp.abs_b + b * ABSORB_BITS + AB_MID + lane;
+    const u64* prev = G + sp.abs_b + (b ? b - 1 : 0) * ABSORB_BITS + AB_MID + 1600 * 24 + lane;      // midRound[24] of block b - 1 (read for b > 0 only)
+    const u64* blk = G + sp.src_b + b * 1088 + lane;                             // KeccakBytes.inBlocks
     u64 bad = 0;
-    // (one state word's ~17 loads per iteration: unrolled, all 400 loads are hoisted -- 256 VGPRs, or 556 B of scratch at 128)
+    // (one row of five state words per iteration, <= 15 loads in flight: unrolled, every load of the block is hoisted)
 #pragma unroll 1
-    for (int i = 0; i < 25; i++) {
-        const u64 st = G[sp.fs_b + b * 1600 + 64 * i + lane];                    // Final.s[b]
-        if (b == 0) bad |= st;                                                     // s[0] <== 0  (:337-341)
-        bad |= G[Ab + 1600 + 64 * i + lane] ^ st;                                  // Absorb.s
-        u64 aux = st;
-        if (i < 17) {
-            const u64 blk = G[sp.src_b + b * 1088 + 64 * i + lane];                // KeccakBytes.inBlocks
-            bad |= (G[sp.kin_b + b * 1088 + 64 * i + lane] ^ blk) | (G[sp.fin_b + b * 1088 + 64 * i + lane] ^ blk) | (G[Ab + 3200 + 64 * i + lane] ^ blk);
-            const u64 o = st ^ blk;
-            const uint32_t X = Ab + ABSORB_OWN + 384 * i;
-            const u64* q = G + X + 192 + 3 * lane;
-            bad |= (G[X + lane] ^ o) | (G[X + 64 + lane] ^ st) | (G[X + 128 + lane] ^ blk) | (q[0] ^ o) | (q[1] ^ st) | (q[2] ^ blk);
-            aux = o;
+    for (int y = 0; y < 5; y++) {
+        u64 m0[5], s[5], k[5];
+#pragma unroll
+        for (int x = 0; x < 5; x++) {
+            const int i = 5 * y + x;
+            m0[x] = mid[64 * i];
+            s[x] = b ? prev[64 * i] : 0;
+            k[x] = i < 17 ? blk[64 * i] : 0;
         }
-        bad |= (G[Ab + 4288 + 64 * i + lane] ^ aux) | (G[Kf + 1600 + 64 * i + lane] ^ aux) | (G[Kf + KF_MID + 64 * i + lane] ^ aux);
-        const u64 last = G[Kf + KF_MID + 1600 * 24 + 64 * i + lane];               // midRound[24]
-        bad |= (G[Kf + 64 * i + lane] ^ last) | (G[Ab + 64 * i + lane] ^ last) | (G[sp.fs_b + (b + 1) * 1600 + 64 * i + lane] ^ last);
+#pragma unroll
+        for (int x = 0; x < 5; x++) bad |= m0[x] ^ s[x] ^ k[x];
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { bad |= ((u64)__shfl_xor((uint32_t)(bad >> 32), o, 64) << 32) | __shfl_xor((uint32_t)bad, o, 64); }
@@ -426,7 +409,7 @@ template <int KR> __device__ __forceinline__ void rounds_gen_body(const KArgs A,
     const uint32_t Ab = sp.abs_b + A.perm_block[pi] * ABSORB_BITS;
     u64* G = A.bits + (uint64_t)y * A.group_stride;
     GenIO io; io.lane = lane;
-    const u64* mid = G + Ab + AB_KECCAKF + KF_MID + 1600 * r0;
+    const u64* mid = G + Ab + AB_MID + 1600 * r0;
 #pragma unroll
     for (int i = 0; i < 25; i++) io.s[i] = mid[64 * i + lane];
     io.st = G + Ab + AB_DIRECT + r0 * KR_BITS;
@@ -457,7 +440,7 @@ template <int KR> __global__ void __launch_bounds__(64) k_rounds_gen(KArgs A) { 
     const uint32_t Ab = sp.abs_b + (A).perm_block[pi] * ABSORB_BITS; \
     const u64* G = (A).bits + (uint64_t)(Y_) * (A).group_stride; \
     CheckIOT<NT, DP> io; io.lane = lane; io.bad = 0; \
-    const u64* mid = G + Ab + AB_KECCAKF + KF_MID + 1600 * r0; \
+    const u64* mid = G + Ab + AB_MID + 1600 * r0; \
     _Pragma("unroll") \
     for (int i = 0; i < 25; i++) io.s[i] = io.ldw(mid + 64 * i + lane); \
     io.st = G + Ab + AB_DIRECT + r0 * KR_BITS; \
@@ -526,7 +509,7 @@ template <int KR, int DP, int WAVES, bool FAULT, bool NTM> __global__ void __lau
     const SpongeDesc sp = A.sponges[A.perm_sponge[pi]];
     const uint32_t Ab = sp.abs_b + A.perm_block[pi] * ABSORB_BITS;
     u64* G = A.bits + (uint64_t)blockIdx.y * A.group_stride;
-    const u64* mid = G + Ab + AB_KECCAKF + KF_MID + 1600 * r0;
+    const u64* mid = G + Ab + AB_MID + 1600 * r0;
     GcIOT<DP, FAULT, NTM> io; io.lane = lane; io.bad = 0;
     if constexpr (FAULT) { io.fault = blockIdx.y == A.fault_group ? G + A.fault_word : nullptr; io.fault_mask = A.fault_mask; }
 #pragma unroll
@@ -551,24 +534,49 @@ template <int KR, int DP, int WAVES, bool FAULT, bool NTM> __global__ void __lau
     }
 }
 
-// the 64-witness word of the wire at offset o of an Absorb block whose storage starts at BIT rank ab (A = this group's slab); *neg: the
-// wire is the complement of that word
-__device__ __forceinline__ u64 absorb_wire_word(const u64* A, uint32_t ab, uint32_t o, const uint16_t* tab, uint32_t* neg) {
+// the 64-witness word of the wire at offset o of an Absorb block (A = this group's slab; B: where the block's sources live); *neg: the wire is
+// the complement of that word.  Ahead of the round blocks (o < AB_ROUNDS_W, keccak.circom:304-323 / :356-367) every wire is a copy of
+//   m0(j) / m24(j): bit j of the block's stored midRound[0] / midRound[24];  s(j): of the previous block's midRound[24], zero for block 0;  k(j): of inBlocks
+//   Absorb:  out@0 = m24 | s@1600 = s | block@3200 = k | aux@4288 = m0 | XorArray i @5888 + 384 i: [out = m0 | a = s | b = k | 64 x (o, a, b)] at 64 i + bit
+//   Keccakf @12416:  out@0 = m24 | in@1600 = m0 | midRound[25]@3200: the stored words themselves
+__device__ __forceinline__ u64 absorb_wire_word(const u64* A, const AbsorbRef B, uint32_t o, const uint16_t* tab, uint32_t* neg) {
     *neg = 0;
-    if (o < AB_DIRECT) return A[ab + o];
-    const uint32_t q = o - AB_DIRECT, r = q / KECCAKF_ROUND_WIRES, e = tab[q - r * KECCAKF_ROUND_WIRES];
+    const uint32_t ab = B.ab;
+    if (o < AB_ROUNDS_W) {
+        enum { M0, M24, S_, K_ };
+        uint32_t what, j;
+        if (o < 1600u) { what = M24; j = o; }
+        else if (o < 3200u) { what = S_; j = o - 1600u; }
+        else if (o < 4288u) { what = K_; j = o - 3200u; }
+        else if (o < ABSORB_OWN) { what = M0; j = o - 4288u; }
+        else if (o < AB_KECCAKF) {
+            const uint32_t q = o - ABSORB_OWN, i = q / 384u, t = q - 384u * i;
+            if (t < 192u) { what = t < 64u ? M0 : t < 128u ? S_ : K_; j = 64u * i + (t & 63u); }
+            else { const uint32_t u = t - 192u, c = u % 3u; what = c == 0 ? M0 : c == 1 ? S_ : K_; j = 64u * i + u / 3u; }
+        } else {
+            const uint32_t q = o - AB_KECCAKF;
+            if (q < 1600u) { what = M24; j = q; }
+            else if (q < KF_MID) { what = M0; j = q - 1600u; }
+            else return A[ab + AB_MID + (q - KF_MID)];
+        }
+        if (what == M0) return A[ab + AB_MID + j];
+        if (what == M24) return A[ab + AB_MID + 1600u * 24u + j];
+        if (what == S_) return B.prev == NO_RANK ? 0 : A[B.prev + j];
+        return A[B.src + j];
+    }
+    const uint32_t q = o - AB_ROUNDS_W, r = q / KECCAKF_ROUND_WIRES, e = tab[q - r * KECCAKF_ROUND_WIRES];
     const uint32_t slot = e >> 7, k = (e >> 1) & 63u;
     *neg = e & 1u;
-    if (slot < KS_ST) return A[ab + AB_KECCAKF + KF_MID + 1600 * r + 64 * slot + k];
+    if (slot < KS_ST) return A[ab + AB_MID + 1600 * r + 64 * slot + k];
     if (slot < KS_OUT) return A[ab + AB_DIRECT + r * KR_BITS + 64 * (slot - KS_ST) + k];
-    if (slot < KS_ZERO) return A[ab + AB_KECCAKF + KF_MID + 1600 * (r + 1) + 64 * (slot - KS_OUT) + k];
+    if (slot < KS_ZERO) return A[ab + AB_MID + 1600 * (r + 1) + 64 * (slot - KS_OUT) + k];
     if (slot == KS_ZERO) return 0;
     return ((KECCAK_RC_DEV[r] >> k) & 1) ? ~0ULL : 0ULL;
 }
 #ifdef POB_KECCAK_TU
 // .wtns expansion of the wires [o0, o0 + count) of ONE Absorb block for witness `sel` of a group: stored wires directly, alias wires through
-// the table (keccak_round_alias_table)
-__global__ void __launch_bounds__(256) k_emit_absorb(const u64* G, uint8_t* out, uint32_t ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab) {
+// the map above and the round blocks' table (keccak_round_alias_table)
+__global__ void __launch_bounds__(256) k_emit_absorb(const u64* G, uint8_t* out, AbsorbRef ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab) {
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) {
         uint32_t neg;
         const u64 word = absorb_wire_word(G, ab, o0 + t, tab, &neg);
@@ -578,7 +586,7 @@ __global__ void __launch_bounds__(256) k_emit_absorb(const u64* G, uint8_t* out,
     }
 }
 // the same for the reduced witness: wires [wire0, wire0 + count) = offsets o0.. of the block, kept wires land at their rank
-__global__ void __launch_bounds__(256) k_emit_absorb_red(const u64* G, uint8_t* out, uint32_t wire0, uint32_t ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab,
+__global__ void __launch_bounds__(256) k_emit_absorb_red(const u64* G, uint8_t* out, uint32_t wire0, AbsorbRef ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab,
                                                          const unsigned long long* rbits, const uint32_t* rpre, uint32_t k0, uint32_t kn) {
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < count; t += gridDim.x * blockDim.x) {
         const uint32_t w = wire0 + t;

@@ -35,6 +35,10 @@ struct KArgs {
     uint32_t fault_group; uint64_t fault_word, fault_mask;   // k_rounds_gc<FAULT> (tests): the store at BIT word fault_word of group fault_group goes out XORed with fault_mask
 };
 
+// where an Absorb block's words live, for the emitter's alias map (keccak_kernels.hpp absorb_wire_word): BIT rank of the block's first stored word, of the previous
+// block's midRound[24] (NO_RANK: block 0 of its sponge, whose input state is zero) and of the block's 1 088 KeccakBytes.inBlocks bits
+struct AbsorbRef { uint32_t ab, prev, src; };
+
 // grid = (nunits, ngroups) wavefronts.  Generation: one kernel per scheduling class (light | SubstringCheck BN254 | the other BN254
 // units at <= 128 VGPRs) + the Poseidon blocks (poseidon_wide.hpp, 8 wavefronts per unit and group); constraint evaluation: one kernel
 // per family (circuits.hpp Fam); emission: light | BN254 | SubstringCheck.
@@ -72,9 +76,9 @@ int pob_kgc_rounds();         // ... of the launch that expands AND evaluates th
 void launch_k_emit_bits(const u64* G, uint8_t* out, uint32_t wire_base, uint32_t bit_base, uint32_t count, uint32_t sel, hipStream_t st);
 // reduced form: wires [wire0, wire0 + count) with BIT ranks from bit_base; kept wires land at out + 32 * (rank - k0) when rank - k0 < kn
 void launch_k_emit_bits_red(const u64* G, uint8_t* out, uint32_t wire0, uint32_t bit_base, uint32_t count, uint32_t sel, const unsigned long long* rbits, const uint32_t* rpre, uint32_t k0, uint32_t kn, hipStream_t st);
-// an Absorb block (circuits.hpp ABSORB_BITS): wires at offsets [o0, o0 + count) of the block whose storage starts at BIT rank ab; tab = the round
-// blocks' alias table on the device (keccak_alias_table_host fills the host copy: KECCAKF_ROUND_WIRES codes, false = the walk is inconsistent)
-void launch_k_emit_absorb(const u64* G, uint8_t* out, uint32_t ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab, hipStream_t st);
-void launch_k_emit_absorb_red(const u64* G, uint8_t* out, uint32_t wire0, uint32_t ab, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab, const unsigned long long* rbits,
+// an Absorb block (circuits.hpp ABSORB_BITS): wires at offsets [o0, o0 + count) of the block B; tab = the round blocks' alias table on the device
+// (keccak_alias_table_host fills the host copy: KECCAKF_ROUND_WIRES codes, false = the walk is inconsistent)
+void launch_k_emit_absorb(const u64* G, uint8_t* out, AbsorbRef B, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab, hipStream_t st);
+void launch_k_emit_absorb_red(const u64* G, uint8_t* out, uint32_t wire0, AbsorbRef B, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab, const unsigned long long* rbits,
                               const uint32_t* rpre, uint32_t k0, uint32_t kn, hipStream_t st);
 bool keccak_alias_table_host(uint16_t* tab);

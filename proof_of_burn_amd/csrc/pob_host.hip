@@ -347,8 +347,8 @@ struct pob_ctx {
         uint64_t pre_made_gen = 0;                       // ... from the resident vector of THIS generation (h->gen_count when the window was expanded)
         std::vector<uint32_t> status_host; uint64_t status_gen = 0;      // the batch's generation statuses, fetched once per generation
         const uint32_t* pin_ptr = nullptr; uint64_t pin_n = 0, pin_id = 0;     // reduced: a map the caller pinned (pob_reduced_map_pin): contents promised unchanged, not hashed again
-        struct Run { uint32_t w, b, n, absorb; };
-        std::vector<Run> runs;                          // the Keccak kernels' wires, sorted by wire index: contiguous stored runs (wire index, BIT rank, count) and Absorb blocks (absorb = 1: stored + alias wires, b = the block's first BIT rank)
+        struct Run { uint32_t w, b, n, absorb, o, prev, src; };
+        std::vector<Run> runs;                          // the Keccak kernels' wires, sorted by wire index: contiguous runs of copies of STORED words (wire index, BIT rank of the source, count) and pieces of Absorb blocks (absorb = 1: stored + alias wires from offset o of the block; b / prev / src = the block's AbsorbRef)
         // which G units write into which window (found by one probe pass per window size): a window launches only those
         uint64_t probe_win = 0, probe_map = 0; uint32_t* d_order = nullptr; unsigned long long* d_probe = nullptr;
         struct WSeg { uint32_t cls, first, count; };
@@ -1349,13 +1349,13 @@ static int emit_make_window(pob_ctx* h, uint32_t idx, uint64_t k, int slot) {
         const uint64_t lo = std::max<uint64_t>(r.w, wire_lo), hi = std::min<uint64_t>((uint64_t)r.w + r.n, wire_hi);
         if (lo >= hi) continue;
         if (!E.red) {
-            if (r.absorb) launch_k_emit_absorb(Gp, E.d_win[slot] + (lo - w0) * 32, r.b, (uint32_t)(lo - r.w), (uint32_t)(hi - lo), idx % 64, h->d_ktab, st);
+            if (r.absorb) launch_k_emit_absorb(Gp, E.d_win[slot] + (lo - w0) * 32, AbsorbRef{r.b, r.prev, r.src}, r.o + (uint32_t)(lo - r.w), (uint32_t)(hi - lo), idx % 64, h->d_ktab, st);
             else launch_k_emit_bits(Gp, E.d_win[slot] + (lo - w0) * 32, 0, (uint32_t)(r.b + (lo - r.w)), (uint32_t)(hi - lo), idx % 64, st);
         } else {
             const auto a = std::lower_bound(E.keep.begin() + w0, E.keep.begin() + w0 + wn, (uint32_t)lo), b = std::lower_bound(a, E.keep.begin() + w0 + wn, (uint32_t)hi);
             if (a == b) continue;                                           // (a round block whose wires are all dropped costs nothing)
             const uint64_t lo2 = *a, hi2 = (uint64_t)*(b - 1) + 1;
-            if (r.absorb) launch_k_emit_absorb_red(Gp, E.d_win[slot], (uint32_t)lo2, r.b, (uint32_t)(lo2 - r.w), (uint32_t)(hi2 - lo2), idx % 64, h->d_ktab, E.d_rbits, E.d_rpre, (uint32_t)w0, (uint32_t)wn, st);
+            if (r.absorb) launch_k_emit_absorb_red(Gp, E.d_win[slot], (uint32_t)lo2, AbsorbRef{r.b, r.prev, r.src}, r.o + (uint32_t)(lo2 - r.w), (uint32_t)(hi2 - lo2), idx % 64, h->d_ktab, E.d_rbits, E.d_rpre, (uint32_t)w0, (uint32_t)wn, st);
             else launch_k_emit_bits_red(Gp, E.d_win[slot], (uint32_t)lo2, (uint32_t)(r.b + (lo2 - r.w)), (uint32_t)(hi2 - lo2), idx % 64, E.d_rbits, E.d_rpre, (uint32_t)w0, (uint32_t)wn, st);
         }
     }
@@ -1455,9 +1455,14 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
             HIPC(hipEventCreateWithFlags(&E.ev_free[k], hipEventDisableTiming));
         }
         for (const SpongeDesc& sp : h->plan.sponges) {
-            E.runs.push_back({sp.kin_w, sp.kin_b, sp.n * 1088, 0}); E.runs.push_back({sp.fin_w, sp.fin_b, sp.n * 1088, 0});
-            E.runs.push_back({sp.fs_w, sp.fs_b, (sp.n + 1) * 1600, 0});
-            for (uint32_t b = 0; b < sp.n; b++) E.runs.push_back({sp.abs_w + b * ABSORB_WIRES, sp.abs_b + b * ABSORB_BITS, ABSORB_WIRES, 1});
+            // Keccak.in / Final.in: copies of KeccakBytes.inBlocks; Final.s[0] = Absorb 0's s (zero: expanded through the block's alias map), Final.s[b + 1] = block b's stored midRound[24]
+            E.runs.push_back({sp.kin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0}); E.runs.push_back({sp.fin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0});
+            E.runs.push_back({sp.fs_w, sp.abs_b, 1600, 1, 1600, NO_RANK, sp.src_b});
+            for (uint32_t b = 0; b < sp.n; b++) {
+                const uint32_t ab = sp.abs_b + b * ABSORB_BITS, m24 = ab + AB_MID + 24u * 1600u;
+                E.runs.push_back({sp.fs_w + (b + 1) * 1600, m24, 1600, 0, 0, 0, 0});
+                E.runs.push_back({sp.abs_w + b * ABSORB_WIRES, ab, ABSORB_WIRES, 1, 0, b ? m24 - ABSORB_BITS : NO_RANK, sp.src_b + b * 1088});
+            }
         }
         std::sort(E.runs.begin(), E.runs.end(), [](const pob_ctx::Emit::Run& a, const pob_ctx::Emit::Run& b) { return a.w < b.w; });
     }
@@ -1942,8 +1947,8 @@ int pob_debug_store_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
         for (const SpongeDesc& sp : h->plan.sponges) {
             if (index < sp.abs_b || index >= sp.abs_b + (uint64_t)sp.n * ABSORB_BITS) continue;
             const uint32_t b = (uint32_t)((index - sp.abs_b) / ABSORB_BITS), o = (uint32_t)((index - sp.abs_b) % ABSORB_BITS);
-            if (o < AB_DIRECT) break;          // (the sponge chain's own words: their evaluation is a launch of pob_constraint_check, k_chain_check)
-            if (wire) *wire = sp.abs_w + b * ABSORB_WIRES + AB_DIRECT + (o - AB_DIRECT) / KR_BITS * KECCAKF_ROUND_WIRES;     // (AB_DIRECT: every wire of the block ahead of the round blocks is stored, so it is their wire offset too)
+            if (o < AB_DIRECT) break;          // (the sponge chain's own words, midRound[0..24]: their evaluation is a launch of pob_constraint_check, k_chain_check)
+            if (wire) *wire = sp.abs_w + b * ABSORB_WIRES + AB_ROUNDS_W + (o - AB_DIRECT) / KR_BITS * KECCAKF_ROUND_WIRES;     // (the round block's first wire: AB_ROUNDS_W wires lie ahead of the round blocks, AB_DIRECT stored words)
             found = true; break;
         }
     } else if (cls == POB_CLASS_SM && h->circuit == POB_CIRCUIT_PROOF_OF_BURN) {
@@ -2053,6 +2058,11 @@ int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t
     }
     if (n == "commitment") { const FrRef r = h->circuit == POB_CIRCUIT_PROOF_OF_BURN ? L.pm.commitment : L.sm.commitment; return set(POB_CLASS_FR, r.i, r.w); }
     if (n == "kb.inLen") { if (k >= L.nkb) return POB_E_ARG; return set(POB_CLASS_SM, L.kbs[k].inLen.i, L.kbs[k].inLen.w); }
+    if (n == "kb.inBlocks" || n == "kb.absorb") {         // of KeccakBytes instance k: the first bit of inBlocks | the first stored word of its first Absorb block (midRound[0][0][0]; block b: + b * ABSORB_BITS) and the block's first wire
+        if (k >= L.nkb) return POB_E_ARG;
+        const KBRefs& r = L.kbs[k];
+        return n == "kb.inBlocks" ? set(POB_CLASS_BIT, r.inBlocks.i, r.inBlocks.w) : set(POB_CLASS_BIT, r.abs_b + AB_MID, r.abs_w);
+    }
     if (n == "pad.div.out" || n == "pad.div.rem") {       // of KeccakBytes instance k
         if (k >= L.nkb) return POB_E_ARG;
         const KBRefs& r = L.kbs[k];

@@ -30,7 +30,9 @@
 //        and the products temps[][] / temp[][] of ShiftRight / ShiftLeft (isEq[i] * in[j]) and parts[] of CompConstant: 3.54 M derived wires in all.
 //   AL   wires (ALIAS, round 4): the wires of a KeccakfRound block other than its 76 stored gate-output arrays -- copies of a stored array / of the round's
 //        input or output state, possibly rotated or negated, or constants.  skip_alias() advances the wire index only; keccak_kernels.hpp names each of
-//        them once (the walker that generates and evaluates, run on a symbolic value type) and the emitter expands through that table.  197 M wires.
+//        them once (the walker that generates and evaluates, run on a symbolic value type) and the emitter expands through that table.  The wires of an
+//        Absorb block AHEAD of its round blocks are aliases too, all but Keccakf's midRound[0..24] (the XorArray outputs and the rounds' outputs): copies of
+//        those words, of the previous block's midRound[24] or of KeccakBytes.inBlocks (keccak_kernels.hpp absorb_wire_word).  198 M wires.
 //
 // Storage index of a wire = its rank among the wires of its class in wire order, so any contiguous
 // run of same-class wires (e.g. a whole Keccak-f block, 2 506 944 BIT wires) is contiguous in HBM.
