@@ -286,6 +286,41 @@ int pob_write_wtns_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint
 int pob_emit_measure_packed(pob_handle h, uint32_t first_idx, uint32_t count, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
                             double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes);
 
+/* GROUP EMISSION.  A payload kind of its own: the packed windows (format version 1, unchanged) of every selected witness of ONE group of 64 -- witnesses 64 * group .. + 63, one
+ * wavefront of the resident vector -- from a single pass over that vector.  Each witness' window is byte for byte what pob_emit_begin_packed / pob_emit_next_packed hands out for
+ * that witness at the same window size and map; pob_unpack_window and every reader of the format work on it untouched.  The single-witness paths rebuild all 64 witnesses of the
+ * group for every witness they emit and keep one; here the Keccak runs' 64-wire blocks (97.5 % of an O0 payload) go from the resident words straight into the 64 tag planes (a
+ * 64 x 64 bit transposition; their canonical form is never written), everything else is written once for all lanes and packed with a witness dimension.
+ * pob_emit_begin_group_packed:
+ *   lanes         bit l selects witness 64 * group + l.  0 = every witness of the group that exists in the current batch and whose generation status is 0; *lanes_out = the mask
+ *                 used (an empty one: the first pob_emit_next_group_packed returns n_wires = 0).  A non-zero mask that names a witness beyond the batch or a failed one:
+ *                 POB_E_STATE, as the single-witness paths refuse it.  An unselected lane costs no PCIe bytes.
+ *   keep, n_keep  NULL, 0: the O0 payload; else the reduced one, with the rules, validation and pinning (pob_reduced_map_pin) of pob_emit_begin_reduced.
+ *   window_wires  payload positions per window; 0 = 4 Mi (4 194 304).  Memory, allocated with the first group emission at a window size w (and kept until a larger one is asked
+ *                 for), fixed(w) = 32 + pad32(16 * ceil(w / 64)) + pad32(8 * ceil(w / 4096)) ~ 0.252 w:
+ *                   device   64 * 32 w (the group's canonical scratch) + 2 * 64 * (32 w + fixed(w) + 32) (two sets of 64 packed windows of any content)
+ *                            + 64 * 4 * (ceil(w / 64) + ceil(w / 4096)) (the scan's rows)  ~ 6 177 bytes per window wire: 24.1 GiB at the default, 6.0 GiB at w = 1 Mi
+ *                   pinned   3 slots, each nsel * fixed(w) + the value sections as the nsel headers count them (+ 1/8), grown on demand: ~ 0.26 bytes per wire, witness and slot for an
+ *                            O0 payload -- never 64 canonical windows
+ *                 POB_E_NOMEM where either allocation fails (nothing of the emission is kept; a smaller window_wires needs proportionally less).
+ *   POB_E_STATE while pob_emit_selfcheck is on: the self-check of group emissions is not implemented (out of scope), switch it off first; and on a handle opened on a
+ *   gadget-level main (pob_gadget_template), which has no group emitter.  An empty mask allocates nothing.  pob_debug_emit_counters counts the single-witness emitter's wires
+ *   only: a group emission leaves the counters as they are.
+ * pob_emit_next_group_packed: data[l] / bytes[l] = witness l's complete packed window in pinned memory owned by the handle, valid until the following call; NULL / 0 for an
+ *   unselected lane.  n_wires = 0 ends the group.  Window k + 1 is expanded while k is copied and k - 1 is with the caller.
+ * Kind rules: pob_emit_next / pob_emit_next_packed after a group begin are POB_E_STATE, and so is pob_emit_next_group_packed after a begin of another kind; a first window
+ * pre-made by pob_emit_queue for another kind is not used, and pob_emit_queue does not reach across groups. */
+int pob_emit_begin_group_packed(pob_handle h, uint32_t group, uint64_t lanes, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires, uint64_t* lanes_out);
+int pob_emit_next_group_packed(pob_handle h, const uint8_t* data[64], uint64_t bytes[64], uint64_t* first_wire, uint64_t* n_wires);
+/* The iden3 .wtns file of every selected lane (lanes, keep: as above) from one group emission, each the same bytes as pob_write_wtns / pob_write_wtns_reduced for that witness;
+ * the host side expands with pob_unpack_window.  paths[l] of an unselected lane is ignored (may be NULL); on an error no file is left behind. */
+int pob_write_wtns_group(pob_handle h, uint32_t group, uint64_t lanes, const uint32_t* keep, uint64_t n_keep, const char* const paths[64]);
+/* Measurement, pob_emit_measure_packed per group: `count` groups from first_group, each with the mask `lanes`; *seconds_pinned = until every window of every selected witness is
+ * in pinned memory, *d2h_bytes = the bytes copied device-to-host for them (the sum of the windows' lengths); dst != NULL (dst_cap >= one window of 32-byte values): a second pass
+ * that also expands every witness' every window into dst gives *seconds_expanded. */
+int pob_emit_measure_group(pob_handle h, uint32_t first_group, uint32_t count, uint64_t lanes, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
+                           double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes);
+
 /* Measurement: average duration (ms, HIP events on `stream`) of `iters` back-to-back launches of one kernel over
  * the current batch.  which: 0 = Keccak round expansion (generate), 1 = Keccak round constraint evaluation,
  * 2 = G-unit constraint evaluation (every family, back to back), 3 = sponge chain (generate); 100 + k / 200 + k = evaluation /

@@ -1023,12 +1023,12 @@ template <class P, uint32_t MASK> GD void unit_run(P& p, const UnitDesc& d, Circ
                 iseq_derived(p, c, (S)i, (S)lastIdx);
                 const F t1 = fr_mul(subNum, p.k256(i)), t2 = fr_mul(fr_to_mont(win), p.k256(i)), dd = fr_sub(t2, t1);
                 p.derived_fr(c.w + 7, t1); p.derived_fr(c.w + 8, t2); p.derived_fr(c.w + 10, dd);
-                const F ds = p.bcast_sel(dd);
-                if (ln == t) ddL = ds;
+                if constexpr (P::is_group) p.derived_fr_inv(c.w + 11, dd, true);       // group emission: every witness' own inverse, nothing to spread (64 x cnt inversions per unit on 64 lanes)
+                else { const F ds = p.bcast_sel(dd); if (ln == t) ddL = ds; }
             }
             sc_window_step(win, sl, (uint32_t)nxt);
         }
-        if constexpr (P::is_emit) {      // the cnt inverses of the emitted witness: one per lane, ONE inversion time per unit (a lane at a time they were 10 ms per unit)
+        if constexpr (P::is_emit) if constexpr (!P::is_group) {      // the cnt inverses of the emitted witness: one per lane, ONE inversion time per unit (a lane at a time they were 10 ms per unit)
             const F inv = fr_is_zero(ddL) ? fr_zero() : fr_inv(ddL);
             if (ln < cnt) p.w32(cur_add(cur_add(sc.c_loop, FP_ISEQ_S, lo + ln), FP_ISEQ_F, lo + ln).w + 11, fr_from_mont(inv), (fr_is_zero(ddL) ? 3 : 2) | 4);      // (counted: pob_debug_emit_counters)
         }

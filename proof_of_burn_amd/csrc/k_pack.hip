@@ -117,6 +117,121 @@ void launch_pack_window(const uint8_t* win, uint64_t first_wire, uint32_t n, uin
     hipLaunchKernelGGL(k_pack_scatter, dim3(grid), dim3(256), 0, st, w4, n, pk, pre);
 }
 
+// ------------------------------------------------------------------------------------------------ the pack pass over the 64 windows of a group emission
+// The four kernels above with a witness dimension: blockIdx.y = rank of the witness among the selected ones (an unselected witness launches nothing); canonical window at
+// win + l * plane, packed form at pk + l * pk_stride, scratch rows blk_pre[l][nblk] and chunk_tot[l][nchunk].  The blocks that the Keccak runs' direct route wrote
+// (k_emit_group.hip: plane words in place, hi = 0, no canonical form) are not launched over at all: fill, classification and scatter run over the block ranges
+// [b0, b1) BETWEEN them, which the host knows; the scan reads the planes only and counts nothing for a direct block.
+__device__ __forceinline__ uint32_t pk_lane_of_rank(u64 lanes, uint32_t r) { for (uint32_t k = 0; k < r; k++) lanes &= lanes - 1; return (uint32_t)__builtin_ctzll(lanes); }
+__global__ void __launch_bounds__(256) k_fill_ee_group(PackGroup g, uint32_t p0, uint32_t p1, bool one_at_0) {
+    const uint32_t l = pk_lane_of_rank(g.lanes, blockIdx.y);
+    const uint64_t i = (uint64_t)p0 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p1) return;
+    uint4* q = (uint4*)(g.win + (uint64_t)l * g.plane) + 2 * i;
+    if (i == 0 && one_at_0) { q[0] = make_uint4(1, 0, 0, 0); q[1] = make_uint4(0, 0, 0, 0); return; }       // wire 0 of the payload is the constant 1
+    q[0] = q[1] = make_uint4(0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu);
+}
+// p0 is a multiple of 64: a wavefront is one block of the window; p1 = the range's end, cut to the window's n
+__global__ void __launch_bounds__(256) k_pack_classify_group(PackGroup g, uint32_t p0, uint32_t p1) {
+    const uint32_t l = pk_lane_of_rank(g.lanes, blockIdx.y);
+    const uint64_t i = (uint64_t)p0 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint4* win = (const uint4*)(g.win + (uint64_t)l * g.plane);
+    uint32_t tag = 0;
+    if (i < p1) {
+        const uint4 a = win[2 * i], b = win[2 * i + 1];
+        const bool narrow = (a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0;
+        tag = !narrow ? 3u : a.x < 2u ? a.x : 2u;
+    }
+    const u64 lo = __ballot((tag & 1u) != 0), hi = __ballot((tag >> 1) != 0);
+    uint4* planes = (uint4*)(g.pk + (uint64_t)l * g.pk_stride + 32);
+    if ((threadIdx.x & 63u) == 0 && i < p1) planes[i >> 6] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+__global__ void __launch_bounds__(64) k_pack_scan_chunk_group(PackGroup g, uint32_t nblk, uint32_t nchunk) {
+    const uint32_t l = pk_lane_of_rank(g.lanes, blockIdx.y);
+    const u64* planes = (const u64*)(g.pk + (uint64_t)l * g.pk_stride + 32);
+    const uint32_t lane = threadIdx.x & 63u, b = blockIdx.x * 64 + lane;
+    uint32_t c = 0;
+    if (b < nblk) { const u64 lo = planes[2 * (uint64_t)b], hi = planes[2 * (uint64_t)b + 1]; c = (uint32_t)__popcll(hi & ~lo) | (uint32_t)__popcll(hi & lo) << 16; }
+    uint32_t inc = c;
+    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl(inc, (lane - d) & 63u, 64); if (lane >= d) inc += t; }
+    if (b < nblk) g.blk_pre[(uint64_t)l * nblk + b] = inc - c;
+    if (lane == 63) g.chunk_tot[(uint64_t)l * nchunk + blockIdx.x] = inc;
+}
+// one wavefront per selected witness; the header also goes to hdr[rank]: the headers cross PCIe as one piece, ahead of the windows
+__global__ void __launch_bounds__(64) k_pack_scan_top_group(PackGroup g, uint64_t first_wire, uint32_t n) {
+    const uint32_t l = pk_lane_of_rank(g.lanes, blockIdx.x);
+    uint8_t* pk = g.pk + (uint64_t)l * g.pk_stride;
+    const uint32_t lane = threadIdx.x & 63u, nblk = (n + 63) / 64, nchunk = (n + 4095) / 4096;
+    const uint32_t* chunk_tot = g.chunk_tot + (uint64_t)l * nchunk;
+    uint32_t* idx = (uint32_t*)(pk + pk_idx_off(n));
+    uint32_t cs = 0, cw = 0;
+    for (uint32_t base = 0; base < nchunk; base += 64) {
+        const uint32_t c = base + lane, t = c < nchunk ? chunk_tot[c] : 0, s = t & 0xFFFFu, w = t >> 16;
+        uint32_t is = s, iw = w;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t ts = __shfl(is, (lane - d) & 63u, 64), tw = __shfl(iw, (lane - d) & 63u, 64);
+            if (lane >= d) { is += ts; iw += tw; }
+        }
+        if (c < nchunk) { idx[2 * (uint64_t)c] = cs + is - s; idx[2 * (uint64_t)c + 1] = cw + iw - w; }
+        cs += __shfl(is, 63, 64); cw += __shfl(iw, 63, 64);
+    }
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    if (lane == 0) {
+        uint4* hd = (uint4*)g.hdr + 2 * blockIdx.x;
+        ((uint4*)pk)[0] = hd[0] = make_uint4(PK_MAGIC, PK_VERSION, (uint32_t)first_wire, (uint32_t)(first_wire >> 32));
+        ((uint4*)pk)[1] = hd[1] = make_uint4(n, cs, cw, 0);
+    }
+    if (lane == 1 && (nblk & 1u)) ((uint4*)(pk + 32))[nblk] = zero;
+    const uint32_t ipad = (uint32_t)((pk_pad32(8 * (uint64_t)nchunk) - 8 * (uint64_t)nchunk) / 4);
+    if (lane < ipad) idx[2 * (uint64_t)nchunk + lane] = 0;
+    const uint32_t spad = (uint32_t)((pk_pad32(4 * (uint64_t)cs) - 4 * (uint64_t)cs) / 4);
+    if (lane < spad) ((uint32_t*)(pk + pk_fixed(n)))[(uint64_t)cs + lane] = 0;
+}
+__global__ void __launch_bounds__(256) k_pack_scatter_group(PackGroup g, uint32_t n, uint32_t p0, uint32_t p1) {
+    const uint32_t l = pk_lane_of_rank(g.lanes, blockIdx.y);
+    const uint64_t i = (uint64_t)p0 + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p1) return;
+    uint8_t* pk = g.pk + (uint64_t)l * g.pk_stride;
+    const uint64_t b = i >> 6; const uint32_t lane = (uint32_t)i & 63u;
+    const u64* planes = (const u64*)(pk + 32);
+    const u64 lo = planes[2 * b], hi = planes[2 * b + 1];
+    if (!((hi >> lane) & 1)) return;
+    const uint4* win = (const uint4*)(g.win + (uint64_t)l * g.plane);
+    const uint32_t* idx = (const uint32_t*)(pk + pk_idx_off(n));
+    const uint32_t pre = g.blk_pre[(uint64_t)l * ((n + 63) / 64) + b];
+    const u64 below = ((u64)1 << lane) - 1;
+    uint8_t* vals = pk + pk_fixed(n);
+    if (!((lo >> lane) & 1)) {
+        const uint64_t r = (uint64_t)idx[2 * (i >> 12)] + (pre & 0xFFFFu) + (uint32_t)__popcll(hi & ~lo & below);
+        ((uint32_t*)vals)[r] = win[2 * i].x;
+    } else {
+        const uint32_t n_small = ((const uint32_t*)pk)[5];
+        const uint64_t r = (uint64_t)idx[2 * (i >> 12) + 1] + (pre >> 16) + (uint32_t)__popcll(hi & lo & below);
+        uint4* dst = (uint4*)(vals + pk_pad32(4 * (uint64_t)n_small)) + 2 * r;
+        dst[0] = win[2 * i]; dst[1] = win[2 * i + 1];
+    }
+}
+void launch_group_fill(const PackGroup& g, uint32_t n, bool one_at_0, const std::vector<std::pair<uint32_t, uint32_t>>& ranges, hipStream_t st) {
+    const uint32_t nsel = (uint32_t)__builtin_popcountll(g.lanes);
+    for (const std::pair<uint32_t, uint32_t>& r : ranges) {
+        const uint32_t p0 = r.first * 64, p1 = r.second * 64 < n ? r.second * 64 : n;
+        hipLaunchKernelGGL(k_fill_ee_group, dim3((p1 - p0 + 255) / 256, nsel), dim3(256), 0, st, g, p0, p1, one_at_0);
+    }
+}
+void launch_pack_group(const PackGroup& g, uint64_t first_wire, uint32_t n, const std::vector<std::pair<uint32_t, uint32_t>>& ranges, hipStream_t st) {
+    const uint32_t nblk = (n + 63) / 64, nchunk = (n + 4095) / 4096, nsel = (uint32_t)__builtin_popcountll(g.lanes);
+    for (const std::pair<uint32_t, uint32_t>& r : ranges) {
+        const uint32_t p0 = r.first * 64, p1 = r.second * 64 < n ? r.second * 64 : n;
+        hipLaunchKernelGGL(k_pack_classify_group, dim3((p1 - p0 + 255) / 256, nsel), dim3(256), 0, st, g, p0, p1);
+    }
+    hipLaunchKernelGGL(k_pack_scan_chunk_group, dim3(nchunk, nsel), dim3(64), 0, st, g, nblk, nchunk);
+    hipLaunchKernelGGL(k_pack_scan_top_group, dim3(nsel), dim3(64), 0, st, g, first_wire, n);
+    for (const std::pair<uint32_t, uint32_t>& r : ranges) {
+        const uint32_t p0 = r.first * 64, p1 = r.second * 64 < n ? r.second * 64 : n;
+        hipLaunchKernelGGL(k_pack_scatter_group, dim3((p1 - p0 + 255) / 256, nsel), dim3(256), 0, st, g, n, p0, p1);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host expansion
 namespace {
 inline uint32_t ld32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }

@@ -23,6 +23,7 @@ struct GArgs {
     uint32_t* emit_sites; uint32_t emit_sites_cap;     // self-check site-recording pass (policy.hpp EmitP::sites)
     uint32_t* emit_counters;                           // which of the emitter's inverse paths ran (policy.hpp EmitP::ctr, pob_debug_emit_counters)
     uint32_t fault_cls, fault_group, fault_idx; uint64_t fault_lanes;      // pob_debug_store_fault (tests): the riding kernels' FAULT instantiations (policy.hpp GenPT<true, true>, poseidon_wide.hpp); fault_cls 0xFFFFFFFF = none
+    uint64_t emit_plane, emit_lanes;                   // group emission (policy.hpp EmitPT<true>): witness l's canonical window at emit_out + l * emit_plane; bit l = witness l is emitted
 };
 struct KArgs {
     u64* bits;                 // BIT slabs, all groups
@@ -61,6 +62,10 @@ void launch_g_check_n2b(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipSt
 void launch_g_emit_light(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
 void launch_g_emit_heavy(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
 void launch_g_emit_sc(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
+// the group emitter (policy.hpp EmitPT<true>): the same units, every selected witness of A.emit_group at once
+void launch_g_emit_group_light(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
+void launch_g_emit_group_heavy(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
+void launch_g_emit_group_sc(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
 // gadget-level mains (gadget_mains.hpp): generation / evaluation / emission of family F_GM on the policies that resolve input references
 void launch_g_gen_gm(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
 void launch_g_check_gm(const GArgs& A, uint32_t nunits, uint32_t ngroups, hipStream_t st);
@@ -82,3 +87,13 @@ void launch_k_emit_absorb(const u64* G, uint8_t* out, AbsorbRef B, uint32_t o0, 
 void launch_k_emit_absorb_red(const u64* G, uint8_t* out, uint32_t wire0, AbsorbRef B, uint32_t o0, uint32_t count, uint32_t sel, const uint16_t* tab, const unsigned long long* rbits,
                               const uint32_t* rpre, uint32_t k0, uint32_t kn, hipStream_t st);
 bool keccak_alias_table_host(uint16_t* tab);
+// ---- group emission (k_emit_group.hip): the Keccak runs' wires for every witness of `lanes` at once.  GroupWin: the group's canonical scratch (witness l's window at
+// win + l * plane, positions [k0, k0 + kn) of the payload) and, reduced form, the map (null: O0, position = wire index)
+struct GroupWin { uint8_t* win; uint64_t plane, lanes; uint32_t k0, kn; const unsigned long long* rbits; const uint32_t* rpre; };
+// wires [wire0, wire0 + count): BIT ranks from bit_base (tab == nullptr) or the offsets o0.. of the Absorb block B, in canonical form (run edges, the reduced form)
+void launch_k_emit_group_canon(const u64* G, GroupWin W, uint32_t wire0, AbsorbRef B, uint32_t o0_or_bit_base, uint32_t count, const uint16_t* tab, hipStream_t st);
+// O0 form, 64-wire blocks [blk0, blk0 + nblk) of the window that lie wholly inside one run: the stored words transposed across the wavefront ARE the witnesses' `lo` tag words
+// (hi = 0); witness l's go to pk + l * pk_stride + 32 + 16 * block (the pack pass is not launched over these blocks).  o0_or_bit_base: of the
+// wire at block blk0's first position
+void launch_k_emit_group_direct(const u64* G, uint8_t* pk, uint64_t pk_stride, uint64_t lanes, uint32_t blk0, uint32_t nblk, AbsorbRef B, uint32_t o0_or_bit_base,
+                                const uint16_t* tab, hipStream_t st);

@@ -370,6 +370,17 @@ struct pob_ctx {
         // (every pack pass runs on the handle's own stream).  pk_d2h: bytes the packed emissions of this handle have copied to the host
         bool packed = false, pre_made_packed = false; uint8_t* d_pk[NSLOT] = {nullptr, nullptr, nullptr}; uint32_t *d_pk_blk = nullptr, *d_pk_tot = nullptr; uint64_t pk_alloc_wires = 0, pk_d2h = 0;
         hipStream_t s_val = nullptr;
+        // GROUP EMISSION (pob_emit_begin_group_packed): a payload kind of its own -- the packed windows of every selected witness of one group of 64 from a single pass over the
+        // resident vector.  d_win: the group's canonical scratch, witness l's window at d_win + l * plane (only the blocks that do not come straight from the Keccak runs are
+        // ever touched); d_pk[2]: the 64 packed windows (stride pk_stride) of the window being expanded and of the one being copied; h_pin[3]: the selected witnesses' complete
+        // packed windows, back to back, sized from the fixed parts plus the counts of the headers (h_hdr: those headers, which cross first); the third one is with the caller
+        struct Group {
+            bool on = false; uint32_t group = 0, nsel = 0; uint64_t lanes = 0, alloc_wires = 0, plane = 0, pk_stride = 0, next_bulk = 0;
+            uint8_t *d_win = nullptr, *d_pk[2] = {nullptr, nullptr}, *d_hdr[2] = {nullptr, nullptr}, *h_hdr[2] = {nullptr, nullptr}, *h_pin[3] = {nullptr, nullptr, nullptr};
+            uint64_t pin_cap[3] = {0, 0, 0}, off[3][64], len[3][64];
+            uint32_t *d_blk = nullptr, *d_tot = nullptr;
+            hipEvent_t ev_made[2] = {nullptr, nullptr}, ev_hdr[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_copied[3] = {nullptr, nullptr, nullptr};
+        } grp;
     } em;
     // schedule
     std::vector<uint32_t> order;                       // unit indices grouped by (stage, lds flag)
@@ -485,6 +496,9 @@ static void launch_g_check(const GArgs& A, uint32_t fam, uint32_t nunits, uint32
     case F_GM: launch_g_check_gm(A, nunits, ngroups, st); break;
     default: launch_g_check_n2b(A, nunits, ngroups, st); break;
     }
+}
+static void launch_g_emit_group(const GArgs& A, uint32_t cls, uint32_t nunits, hipStream_t st) {
+    if (cls == 3) launch_g_emit_group_sc(A, nunits, 1, st); else if (cls) launch_g_emit_group_heavy(A, nunits, 1, st); else launch_g_emit_group_light(A, nunits, 1, st);
 }
 static void launch_g_emit(const GArgs& A, uint32_t cls, uint32_t nunits, hipStream_t st) {
     if (cls == 5) launch_g_emit_gm(A, nunits, 1, st); else if (cls == 3) launch_g_emit_sc(A, nunits, 1, st); else if (cls) launch_g_emit_heavy(A, nunits, 1, st); else launch_g_emit_light(A, nunits, 1, st);
@@ -866,12 +880,25 @@ int pob_open(int device, int circuit, const uint64_t* params, int nparams, uint3
     return POB_OK;
 }
 
+// the window-sized buffers of the group emission: freed and forgotten (no early return: every pointer is null afterwards, whatever a free reports)
+static void group_free_device(pob_ctx::Emit::Group& Gr) {
+    for (void* p : {(void*)Gr.d_win, (void*)Gr.d_pk[0], (void*)Gr.d_pk[1], (void*)Gr.d_hdr[0], (void*)Gr.d_hdr[1], (void*)Gr.d_blk, (void*)Gr.d_tot}) if (p) (void)hipFree(p);
+    for (uint8_t* p : {Gr.h_hdr[0], Gr.h_hdr[1]}) if (p) (void)hipHostFree(p);
+    Gr.d_win = Gr.d_pk[0] = Gr.d_pk[1] = Gr.d_hdr[0] = Gr.d_hdr[1] = Gr.h_hdr[0] = Gr.h_hdr[1] = nullptr; Gr.d_blk = Gr.d_tot = nullptr; Gr.alloc_wires = 0;
+}
+
 void pob_close(pob_handle h) {
     if (!h) return;
     hipSetDevice(h->device);
     void* ptrs[] = {h->d_bits, h->d_sm, h->d_fr, h->d_units, h->d_order, h->d_L, h->d_sponges, h->d_perm_sponge, h->d_perm_block, h->d_pos,
                     h->d_inv, h->d_pow256, h->d_ktab, h->d_emit_ctr, h->d_in_fr[0], h->d_in_fr[1], h->d_in_sm[0], h->d_in_sm[1], h->d_in_sm8[0], h->d_in_sm8[1], h->d_in_exc[0], h->d_in_exc[1], h->d_status_raw, h->d_status, h->d_chk, h->d_bad, h->d_outputs, h->d_records, h->em.d_win[0], h->em.d_win[1], h->em.d_win[2], h->em.d_order, h->em.d_probe, h->em.d_rbits, h->em.d_rpre, h->em.d_sc_z, h->em.d_sc_m, h->em.d_sc_c, h->em.d_sc_res, h->em.d_sc_zr, h->em.d_sc_mr, h->em.d_pk[0], h->em.d_pk[1], h->em.d_pk[2], h->em.d_pk_blk, h->em.d_pk_tot};
     for (void* p : ptrs) if (p) hipFree(p);
+    {
+        pob_ctx::Emit::Group& Gr = h->em.grp;
+        group_free_device(Gr);
+        for (int k = 0; k < 3; k++) if (Gr.h_pin[k]) hipHostFree(Gr.h_pin[k]);
+        for (hipEvent_t e : {Gr.ev_made[0], Gr.ev_made[1], Gr.ev_hdr[0], Gr.ev_hdr[1], Gr.ev_free[0], Gr.ev_free[1], Gr.ev_copied[0], Gr.ev_copied[1], Gr.ev_copied[2]}) if (e) hipEventDestroy(e);
+    }
     for (int k = 0; k < pob_ctx::Emit::NSLOT; k++) {
         if (h->em.h_pin[k]) hipHostFree(h->em.h_pin[k]);
         for (hipEvent_t e : {h->em.ev_made[k], h->em.ev_copied[k], h->em.ev_free[k]}) if (e) hipEventDestroy(e);
@@ -1423,6 +1450,35 @@ static int emit_statuses(pob_ctx* h) {
     return POB_OK;
 }
 
+// the copy stream, the slots' events and the Keccak kernels' runs: once per handle; the copies of a previous emission (an abandoned one, a discarded first window) are waited for
+static int emit_streams_and_runs(pob_ctx* h) {
+    pob_ctx::Emit& E = h->em;
+    const int NS = pob_ctx::Emit::NSLOT;
+    if (E.s_copy) HIPC(hipStreamSynchronize(E.s_copy));
+    if (!E.s_copy) {
+        HIPC(hipStreamCreateWithPriority(&E.s_copy, hipStreamNonBlocking, 0));
+        for (int k = 0; k < NS; k++) {
+            HIPC(hipEventCreateWithFlags(&E.ev_made[k], hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&E.ev_copied[k], hipEventDisableTiming));
+            HIPC(hipEventCreateWithFlags(&E.ev_free[k], hipEventDisableTiming));
+        }
+        for (const SpongeDesc& sp : h->plan.sponges) {
+            // Keccak.in / Final.in: copies of KeccakBytes.inBlocks; Final.s[0] = Absorb 0's s (zero: expanded through the block's alias map), Final.s[b + 1] = block b's stored midRound[24]
+            E.runs.push_back({sp.kin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0}); E.runs.push_back({sp.fin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0});
+            E.runs.push_back({sp.fs_w, sp.abs_b, 1600, 1, 1600, NO_RANK, sp.src_b});
+            for (uint32_t b = 0; b < sp.n; b++) {
+                const uint32_t ab = sp.abs_b + b * ABSORB_BITS, m24 = ab + AB_MID + 24u * 1600u;
+                E.runs.push_back({sp.fs_w + (b + 1) * 1600, m24, 1600, 0, 0, 0, 0});
+                E.runs.push_back({sp.abs_w + b * ABSORB_WIRES, ab, ABSORB_WIRES, 1, 0, b ? m24 - ABSORB_BITS : NO_RANK, sp.src_b + b * 1088});
+            }
+        }
+        std::sort(E.runs.begin(), E.runs.end(), [](const pob_ctx::Emit::Run& a, const pob_ctx::Emit::Run& b) { return a.w < b.w; });
+    }
+    return POB_OK;
+}
+
+// which G units write into which window: one probe pass per (window size, map), with the single-witness kernels (what a unit writes does not depend on the witness)
+static int emit_probe_pass(pob_ctx* h, uint32_t group, uint64_t window_wires, uint64_t nwin_);
+
 // common part of pob_emit_begin / pob_emit_begin_reduced: E.red / E.map_id / E.total are set
 static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
     pob_ctx::Emit& E = h->em;
@@ -1442,30 +1498,13 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
     // behind the previous witness' last windows already -- continue from there, nothing to wait for
     if (E.pre_made && E.pre_made_gen == h->gen_count && E.queued_idx == (int64_t)idx && E.win_wires == window_wires && E.nwin == nwin_ && E.probe_map == E.map_id && E.pre_made_packed == E.packed) {
         E.first_slot = (E.first_slot + (uint32_t)E.nwin) % NS;
-        E.idx = idx; E.next_make = 1; E.next_take = 0; E.active = true; E.queued_idx = -1; E.pre_made = false;
+        E.idx = idx; E.next_make = 1; E.next_take = 0; E.active = true; E.queued_idx = -1; E.pre_made = false; E.grp.on = false;
         return POB_OK;
     }
     if (E.pre_made || E.queued_idx == (int64_t)idx) E.queued_idx = -1;      // (an announcement made BEFORE this begin, for the witness after this one, stays)
     E.pre_made = false;
-    if (E.s_copy) HIPC(hipStreamSynchronize(E.s_copy));                    // the copies of a previous witness (an abandoned emission, a discarded first window)
-    if (!E.s_copy) {
-        HIPC(hipStreamCreateWithPriority(&E.s_copy, hipStreamNonBlocking, 0));
-        for (int k = 0; k < NS; k++) {
-            HIPC(hipEventCreateWithFlags(&E.ev_made[k], hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&E.ev_copied[k], hipEventDisableTiming));
-            HIPC(hipEventCreateWithFlags(&E.ev_free[k], hipEventDisableTiming));
-        }
-        for (const SpongeDesc& sp : h->plan.sponges) {
-            // Keccak.in / Final.in: copies of KeccakBytes.inBlocks; Final.s[0] = Absorb 0's s (zero: expanded through the block's alias map), Final.s[b + 1] = block b's stored midRound[24]
-            E.runs.push_back({sp.kin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0}); E.runs.push_back({sp.fin_w, sp.src_b, sp.n * 1088, 0, 0, 0, 0});
-            E.runs.push_back({sp.fs_w, sp.abs_b, 1600, 1, 1600, NO_RANK, sp.src_b});
-            for (uint32_t b = 0; b < sp.n; b++) {
-                const uint32_t ab = sp.abs_b + b * ABSORB_BITS, m24 = ab + AB_MID + 24u * 1600u;
-                E.runs.push_back({sp.fs_w + (b + 1) * 1600, m24, 1600, 0, 0, 0, 0});
-                E.runs.push_back({sp.abs_w + b * ABSORB_WIRES, ab, ABSORB_WIRES, 1, 0, b ? m24 - ABSORB_BITS : NO_RANK, sp.src_b + b * 1088});
-            }
-        }
-        std::sort(E.runs.begin(), E.runs.end(), [](const pob_ctx::Emit::Run& a, const pob_ctx::Emit::Run& b) { return a.w < b.w; });
-    }
+    E.grp.on = false;
+    { int rc = emit_streams_and_runs(h); if (rc) return rc; }
     if (E.alloc_wires < window_wires) {                                     // (re)allocated only when a larger window is asked for: K witnesses reuse the buffers
         for (int k = 0; k < NS; k++) {
             if (E.d_win[k]) { HIPC(hipFree(E.d_win[k])); E.d_win[k] = nullptr; }
@@ -1486,34 +1525,7 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
         if (!E.s_val) HIPC(hipStreamCreateWithPriority(&E.s_val, hipStreamNonBlocking, 0));
         E.pk_alloc_wires = E.alloc_wires;
     }
-    if ((E.probe_win != window_wires || E.probe_map != E.map_id) && nwin_ <= 64) {
-        // probe pass: every G unit runs once with the emitter's stores replaced by "mark window position / window_wires"; a window then
-        // launches only the units that can write into it (most windows hold nothing but Keccak round wires)
-        const size_t nu = h->plan.units.size();
-        if (!E.d_probe) HIPC(hipMalloc(&E.d_probe, nu * 8));
-        HIPC(hipMemsetAsync(E.d_probe, 0, nu * 8, own_stream(h)));
-        GArgs A = gargs(h);
-        A.emit_sel = 0; A.emit_group = idx / 64; A.emit_w0 = 0; A.emit_wn = (uint32_t)window_wires; A.emit_probe = E.d_probe; A.emit_out = nullptr;
-        if (E.red) { A.emit_rbits = E.d_rbits; A.emit_rpre = E.d_rpre; }
-        for (const pob_ctx::Seg& sg : h->emit_segs) { A.first = sg.first; launch_g_emit(A, sg.lds, sg.count, own_stream(h)); }
-        HIPC(hipGetLastError());
-        std::vector<unsigned long long> mask(nu);
-        HIPC(hipMemcpyAsync(mask.data(), E.d_probe, nu * 8, hipMemcpyDeviceToHost, own_stream(h)));
-        HIPC(hipStreamSynchronize(own_stream(h)));
-        std::vector<uint32_t> order;
-        E.wsegs.assign(nwin_, {});
-        for (uint64_t wi = 0; wi < nwin_; wi++)
-            for (const pob_ctx::Seg& sg : h->emit_segs) {
-                pob_ctx::Emit::WSeg ws{sg.lds, (uint32_t)order.size(), 0};
-                for (uint32_t j = 0; j < sg.count; j++) { const uint32_t u = h->order[sg.first + j]; if ((mask[u] >> wi) & 1) order.push_back(u); }
-                ws.count = (uint32_t)order.size() - ws.first;
-                if (ws.count) E.wsegs[wi].push_back(ws);
-            }
-        if (E.d_order) { HIPC(hipFree(E.d_order)); E.d_order = nullptr; }
-        HIPC(hipMalloc(&E.d_order, std::max<size_t>(order.size(), 1) * 4));
-        if (!order.empty()) HIPC(hipMemcpy(E.d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice));
-        E.probe_win = window_wires; E.probe_map = E.map_id;
-    } else if (nwin_ > 64) { E.probe_win = 0; E.probe_map = E.map_id; }       // (too many windows for the probe's 64-bit masks: every unit runs for every window)
+    { int rc = emit_probe_pass(h, idx / 64, window_wires, nwin_); if (rc) return rc; }
     if (E.sc_on && !E.sc_built) {
         // site-recording pass: every emitting unit once with EmitP::sites set (nothing is written); the sites are layout constants of the handle
         const uint32_t cap = std::max(h->plan.total.q, 1u);
@@ -1599,6 +1611,39 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
     return POB_OK;
 }
 
+static int emit_probe_pass(pob_ctx* h, uint32_t group, uint64_t window_wires, uint64_t nwin_) {
+    pob_ctx::Emit& E = h->em;
+    if ((E.probe_win != window_wires || E.probe_map != E.map_id) && nwin_ <= 64) {
+        // probe pass: every G unit runs once with the emitter's stores replaced by "mark window position / window_wires"; a window then
+        // launches only the units that can write into it (most windows hold nothing but Keccak round wires)
+        const size_t nu = h->plan.units.size();
+        if (!E.d_probe) HIPC(hipMalloc(&E.d_probe, nu * 8));
+        HIPC(hipMemsetAsync(E.d_probe, 0, nu * 8, own_stream(h)));
+        GArgs A = gargs(h);
+        A.emit_sel = 0; A.emit_group = group; A.emit_w0 = 0; A.emit_wn = (uint32_t)window_wires; A.emit_probe = E.d_probe; A.emit_out = nullptr;
+        if (E.red) { A.emit_rbits = E.d_rbits; A.emit_rpre = E.d_rpre; }
+        for (const pob_ctx::Seg& sg : h->emit_segs) { A.first = sg.first; launch_g_emit(A, sg.lds, sg.count, own_stream(h)); }
+        HIPC(hipGetLastError());
+        std::vector<unsigned long long> mask(nu);
+        HIPC(hipMemcpyAsync(mask.data(), E.d_probe, nu * 8, hipMemcpyDeviceToHost, own_stream(h)));
+        HIPC(hipStreamSynchronize(own_stream(h)));
+        std::vector<uint32_t> order;
+        E.wsegs.assign(nwin_, {});
+        for (uint64_t wi = 0; wi < nwin_; wi++)
+            for (const pob_ctx::Seg& sg : h->emit_segs) {
+                pob_ctx::Emit::WSeg ws{sg.lds, (uint32_t)order.size(), 0};
+                for (uint32_t j = 0; j < sg.count; j++) { const uint32_t u = h->order[sg.first + j]; if ((mask[u] >> wi) & 1) order.push_back(u); }
+                ws.count = (uint32_t)order.size() - ws.first;
+                if (ws.count) E.wsegs[wi].push_back(ws);
+            }
+        if (E.d_order) { HIPC(hipFree(E.d_order)); E.d_order = nullptr; }
+        HIPC(hipMalloc(&E.d_order, std::max<size_t>(order.size(), 1) * 4));
+        if (!order.empty()) HIPC(hipMemcpy(E.d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+        E.probe_win = window_wires; E.probe_map = E.map_id;
+    } else if (nwin_ > 64) { E.probe_win = 0; E.probe_map = E.map_id; }       // (too many windows for the probe's 64-bit masks: every unit runs for every window)
+    return POB_OK;
+}
+
 int pob_emit_begin(pob_handle h, uint32_t idx, uint64_t window_wires) {
     if (!h) return POB_E_ARG;
     if (!h->generated || idx >= h->n) { h->err = "nothing generated / witness index out of range"; return POB_E_STATE; }
@@ -1618,10 +1663,17 @@ int pob_emit_begin_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint
     return emit_start(h, idx, window_wires);
 }
 
+static int emit_set_map(pob_handle h, const uint32_t* keep, uint64_t n_keep);
 static int emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires, bool packed) {
     if (!h || !keep || n_keep == 0) return POB_E_ARG;
     if (!h->generated || idx >= h->n) { h->err = "nothing generated / witness index out of range"; return POB_E_STATE; }
     HIPC(hipSetDevice(h->device));
+    { int rc = emit_set_map(h, keep, n_keep); if (rc) return rc; }
+    h->em.packed = packed;
+    return emit_start(h, idx, window_wires);
+}
+// the reduced payload's map: validated, uploaded and made the current one (E.red / E.map_id / E.total); the same map again costs its hash, a pinned one nothing
+static int emit_set_map(pob_handle h, const uint32_t* keep, uint64_t n_keep) {
     pob_ctx::Emit& E = h->em;
     const uint64_t W = h->plan.total.w;
     // a map the caller PINNED (pob_reduced_map_pin: same address and length, contents promised unchanged) is not hashed again; any other map is
@@ -1650,8 +1702,8 @@ static int emit_begin_reduced(pob_handle h, uint32_t idx, const uint32_t* keep, 
         E.keep.assign(keep, keep + n_keep);
         E.queued_idx = -1; E.pre_made = false;
     }
-    E.red = true; E.map_id = id; E.total = n_keep; E.packed = packed;
-    return emit_start(h, idx, window_wires);
+    E.red = true; E.map_id = id; E.total = n_keep;
+    return POB_OK;
 }
 
 int pob_reduced_map_pin(pob_handle h, const uint32_t* keep, uint64_t n_keep) {
@@ -1666,6 +1718,7 @@ static int emit_next(pob_handle h, bool packed, const uint8_t** data, uint64_t* 
     if (!h || !data || !first_wire || !n_wires) return POB_E_ARG;
     pob_ctx::Emit& E = h->em;
     if (!E.active) { h->err = "pob_emit_next without pob_emit_begin"; return POB_E_STATE; }
+    if (E.grp.on) { h->err = "pob_emit_next / pob_emit_next_packed: the emission was begun with pob_emit_begin_group_packed"; return POB_E_STATE; }
     if (E.packed != packed) { h->err = packed ? "pob_emit_next_packed: the emission was not begun with pob_emit_begin_packed" : "pob_emit_next: the emission was begun with pob_emit_begin_packed"; return POB_E_STATE; }
     if (E.next_take == E.nwin) { E.active = false; *data = nullptr; *first_wire = E.total; *n_wires = 0; return POB_OK; }
     HIPC(hipSetDevice(h->device));
@@ -1702,6 +1755,183 @@ int pob_emit_next(pob_handle h, const uint8_t** data, uint64_t* first_wire, uint
 int pob_emit_next_packed(pob_handle h, const uint8_t** data, uint64_t* bytes, uint64_t* first_wire, uint64_t* n_wires) {
     if (!bytes) return POB_E_ARG;
     return emit_next(h, true, data, bytes, first_wire, n_wires);
+}
+
+// ---- group emission: the packed windows of every selected witness of ONE group of 64 from a single pass over the resident vector (include/pob_hip.h).
+// Per window: the Keccak runs' 64-wire blocks go straight into the 64 tag planes (k_emit_group.hip: transposition of the stored words, no canonical form), everything else
+// -- the G units on EmitPT<true>, run edges, the whole reduced form -- into the group's canonical scratch, which the pack pass compacts with a witness dimension (k_pack.hip).
+#define GROUP_DEFAULT_WINDOW (4ull << 20)
+static int group_make_window(pob_ctx* h, uint64_t k) {
+    pob_ctx::Emit& E = h->em; pob_ctx::Emit::Group& Gr = E.grp;
+    const int ps = (int)(k % 2);
+    const uint64_t w0 = k * E.win_wires, wn = std::min(E.win_wires, E.total - w0);
+    const uint32_t nblk = (uint32_t)((wn + 63) / 64);
+    hipStream_t st = own_stream(h);
+    HIPC(hipStreamWaitEvent(st, Gr.ev_free[ps], 0));                        // the copies of the window that used this packed slot before are done
+    const u64* Gp = (const u64*)h->d_bits + (uint64_t)Gr.group * h->plan.total.b;
+    const uint64_t wire_lo = E.red ? E.keep[w0] : w0, wire_hi = E.red ? (uint64_t)E.keep[w0 + wn - 1] + 1 : w0 + wn;
+    const GroupWin GW{Gr.d_win, Gr.plane, Gr.lanes, (uint32_t)w0, (uint32_t)wn, E.red ? E.d_rbits : nullptr, E.red ? E.d_rpre : nullptr};
+    struct Piece { const pob_ctx::Emit::Run* r; uint64_t lo, hi; };
+    std::vector<Piece> canon;                                               // what of the runs takes the canonical route, launched behind the fill
+    std::vector<std::pair<uint32_t, uint32_t>> ranges;                      // the block ranges of the window BETWEEN the direct ones: fill and pack pass run over these only
+    uint32_t covered = 0;
+    for (const pob_ctx::Emit::Run& r : E.runs) {
+        uint64_t lo = std::max<uint64_t>(r.w, wire_lo), hi = std::min<uint64_t>((uint64_t)r.w + r.n, wire_hi);
+        if (lo >= hi) continue;
+        if (E.red) {
+            const auto a = std::lower_bound(E.keep.begin() + w0, E.keep.begin() + w0 + wn, (uint32_t)lo), b = std::lower_bound(a, E.keep.begin() + w0 + wn, (uint32_t)hi);
+            if (a == b) continue;
+            canon.push_back({&r, *a, (uint64_t)*(b - 1) + 1});
+            continue;
+        }
+        // O0: the blocks of the window wholly inside the run go straight into the tag planes; the partial blocks at the run's ends (and at a window edge that is no multiple of 64) do not
+        const uint64_t bA = (lo - w0 + 63) / 64, bB = (hi - w0) / 64;
+        if (bB > bA) {
+            const uint64_t wa = w0 + 64 * bA, wb = w0 + 64 * bB;
+            if ((uint32_t)bA > covered) ranges.push_back({covered, (uint32_t)bA});
+            covered = (uint32_t)bB;                                         // (the runs are sorted by wire and do not overlap)
+            launch_k_emit_group_direct(Gp, Gr.d_pk[ps], Gr.pk_stride, Gr.lanes, (uint32_t)bA, (uint32_t)(bB - bA), AbsorbRef{r.b, r.prev, r.src},
+                                       (r.absorb ? r.o : r.b) + (uint32_t)(wa - r.w), r.absorb ? h->d_ktab : nullptr, st);
+            if (lo < wa) canon.push_back({&r, lo, wa});
+            if (wb < hi) canon.push_back({&r, wb, hi});
+        } else canon.push_back({&r, lo, hi});
+    }
+    if (covered < nblk) ranges.push_back({covered, nblk});
+    const PackGroup PG{Gr.d_win, Gr.plane, Gr.d_pk[ps], Gr.pk_stride, Gr.lanes, Gr.d_blk, Gr.d_tot, Gr.d_hdr[ps]};
+    launch_group_fill(PG, (uint32_t)wn, w0 == 0, ranges, st);               // 0xEE.. where no direct block is (a wire nobody owns is not a field element); wire 0 = 1 (always kept)
+    GArgs A = gargs(h);
+    A.emit_out = Gr.d_win; A.emit_plane = Gr.plane; A.emit_lanes = Gr.lanes; A.emit_sel = 0; A.emit_group = Gr.group; A.emit_w0 = (uint32_t)w0; A.emit_wn = (uint32_t)wn;
+    if (E.red) { A.emit_rbits = E.d_rbits; A.emit_rpre = E.d_rpre; }
+    if (E.probe_win == E.win_wires && E.probe_map == E.map_id && k < E.wsegs.size()) {      // only the units that write into this window
+        A.order = E.d_order;
+        for (const pob_ctx::Emit::WSeg& sg : E.wsegs[k]) { A.first = sg.first; launch_g_emit_group(A, sg.cls, sg.count, st); }
+    } else {
+        for (const pob_ctx::Seg& sg : h->emit_segs) { A.first = sg.first; launch_g_emit_group(A, sg.lds, sg.count, st); }
+    }
+    for (const Piece& c : canon) {
+        const pob_ctx::Emit::Run& r = *c.r;
+        launch_k_emit_group_canon(Gp, GW, (uint32_t)c.lo, AbsorbRef{r.b, r.prev, r.src}, (r.absorb ? r.o : r.b) + (uint32_t)(c.lo - r.w), (uint32_t)(c.hi - c.lo), r.absorb ? h->d_ktab : nullptr, st);
+    }
+    launch_pack_group(PG, w0, (uint32_t)wn, ranges, st);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(Gr.ev_made[ps], st));
+    HIPC(hipStreamWaitEvent(E.s_copy, Gr.ev_made[ps], 0));
+    HIPC(hipMemcpyAsync(Gr.h_hdr[ps], Gr.d_hdr[ps], (size_t)Gr.nsel * 32, hipMemcpyDeviceToHost, E.s_copy));     // the headers first: their counts size the windows' copies
+    HIPC(hipEventRecord(Gr.ev_hdr[ps], E.s_copy));
+    return POB_OK;
+}
+
+// the headers of window k are in pinned memory: lay the selected witnesses' windows out back to back in the pinned slot (grown to what the counts ask for) and copy them
+static int group_copy_window(pob_ctx* h, uint64_t k) {
+    pob_ctx::Emit& E = h->em; pob_ctx::Emit::Group& Gr = E.grp;
+    const int ps = (int)(k % 2), hs = (int)(k % 3);
+    const uint64_t wn = std::min(E.win_wires, E.total - k * E.win_wires), fixed = pack_fixed_bytes(wn);
+    HIPC(hipEventSynchronize(Gr.ev_hdr[ps]));
+    uint64_t total = 0; uint32_t r = 0;
+    for (uint32_t l = 0; l < 64; l++) {
+        Gr.off[hs][l] = Gr.len[hs][l] = 0;
+        if (!((Gr.lanes >> l) & 1)) continue;
+        uint32_t cnt[2]; memcpy(cnt, Gr.h_hdr[ps] + 32 * (size_t)r++ + 20, 8);
+        if ((uint64_t)cnt[0] + cnt[1] > wn) { h->err = "internal: packed window counts more values than wires"; return POB_E_STATE; }
+        Gr.off[hs][l] = total; Gr.len[hs][l] = fixed + pack_value_bytes(cnt[0], cnt[1]); total += Gr.len[hs][l];
+    }
+    if (Gr.pin_cap[hs] < total) {
+        if (Gr.h_pin[hs]) { HIPC(hipHostFree(Gr.h_pin[hs])); Gr.h_pin[hs] = nullptr; Gr.pin_cap[hs] = 0; }
+        const uint64_t cap = total + total / 8 + 4096;                     // (the windows of a payload differ in their values: some room, so that not every slightly longer one allocates)
+        if (hipHostMalloc((void**)&Gr.h_pin[hs], cap, hipHostMallocDefault) != hipSuccess) { Gr.h_pin[hs] = nullptr; (void)hipGetLastError(); h->err = "group emission: out of pinned host memory"; E.active = false; return POB_E_NOMEM; }
+        Gr.pin_cap[hs] = cap;
+    }
+    r = 0;
+    for (uint32_t l = 0; l < 64; l++) {
+        if (!Gr.len[hs][l]) continue;
+        uint8_t* dst = Gr.h_pin[hs] + Gr.off[hs][l];
+        memcpy(dst, Gr.h_hdr[ps] + 32 * (size_t)r++, 32);
+        HIPC(hipMemcpyAsync(dst + 32, Gr.d_pk[ps] + (uint64_t)l * Gr.pk_stride + 32, Gr.len[hs][l] - 32, hipMemcpyDeviceToHost, E.s_copy));
+    }
+    E.pk_d2h += total;
+    HIPC(hipEventRecord(Gr.ev_copied[hs], E.s_copy));
+    HIPC(hipEventRecord(Gr.ev_free[ps], E.s_copy));
+    return POB_OK;
+}
+
+int pob_emit_begin_group_packed(pob_handle h, uint32_t group, uint64_t lanes, const uint32_t* keep, uint64_t n_keep, uint64_t window_wires, uint64_t* lanes_out) {
+    if (!h || !lanes_out || (!keep && n_keep) || (keep && !n_keep)) return POB_E_ARG;
+    pob_ctx::Emit& E = h->em; pob_ctx::Emit::Group& Gr = E.grp;
+    if (!h->generated || (uint64_t)group * 64 >= h->n) { h->err = "nothing generated / group out of range"; return POB_E_STATE; }
+    if (E.sc_on) { h->err = "group emissions are not self-checked: switch pob_emit_selfcheck off"; return POB_E_STATE; }
+    for (const pob_ctx::Seg& sg : h->emit_segs) if (sg.lds == 5) { h->err = "group emission is for the circuits' mains, not for gadget-level mains"; return POB_E_STATE; }
+    HIPC(hipSetDevice(h->device));
+    HIPC(hipEventSynchronize(h->ev_gen_done));
+    if (h->evaluated) HIPC(hipEventSynchronize(h->ev_check_done));
+    { int rc = emit_statuses(h); if (rc) return rc; }
+    uint64_t good = 0;                                                      // the witnesses of the group that exist in this batch and passed every assert
+    for (uint32_t l = 0; l < 64 && (uint64_t)group * 64 + l < h->n; l++) if (E.status_host[group * 64 + l] == 0) good |= 1ull << l;
+    if (lanes & ~good) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(lanes & ~good);
+        h->err = "group emission: witness " + std::to_string((uint64_t)group * 64 + l) + " is beyond the batch or failed an assert: nothing to emit";
+        return POB_E_STATE;
+    }
+    if (!lanes) lanes = good;
+    if (keep) { int rc = emit_set_map(h, keep, n_keep); if (rc) return rc; }
+    else { E.red = false; E.map_id = 0; E.total = h->plan.total.w; }
+    E.packed = true; E.queued_idx = -1; E.pre_made = false;                 // (a window pre-made for another kind of emission is not used, an announcement does not carry over)
+    E.active = false;
+    { int rc = emit_streams_and_runs(h); if (rc) return rc; }
+    HIPC(hipStreamSynchronize(own_stream(h)));
+    if (!Gr.ev_made[0]) {
+        for (int k = 0; k < 2; k++) { HIPC(hipEventCreateWithFlags(&Gr.ev_made[k], hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&Gr.ev_hdr[k], hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&Gr.ev_free[k], hipEventDisableTiming)); }
+        for (int k = 0; k < 3; k++) HIPC(hipEventCreateWithFlags(&Gr.ev_copied[k], hipEventDisableTiming));
+    }
+    if (window_wires == 0) window_wires = GROUP_DEFAULT_WINDOW;
+    window_wires = std::min<uint64_t>(window_wires, E.total);
+    const uint64_t nwin_ = (E.total + window_wires - 1) / window_wires;
+    if (lanes && Gr.alloc_wires < window_wires) {                           // device side, as a function of the window size w (include/pob_hip.h): 64 * 32 w scratch, 2 x 64 packed windows of any content, the scan's rows; nothing for an empty mask
+        group_free_device(Gr);
+        Gr.plane = window_wires * 32; Gr.pk_stride = window_wires * 32 + pack_fixed_bytes(window_wires) + 32;
+        const uint64_t nblk = (window_wires + 63) / 64, nchunk = (window_wires + 4095) / 4096;
+        bool ok = hipMalloc(&Gr.d_win, 64 * Gr.plane) == hipSuccess && hipMalloc(&Gr.d_blk, 64 * nblk * 4) == hipSuccess && hipMalloc(&Gr.d_tot, 64 * nchunk * 4) == hipSuccess;
+        for (int k = 0; k < 2 && ok; k++)
+            ok = hipMalloc(&Gr.d_pk[k], 64 * Gr.pk_stride) == hipSuccess && hipMalloc(&Gr.d_hdr[k], 64 * 32) == hipSuccess && hipHostMalloc((void**)&Gr.h_hdr[k], 64 * 32, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            group_free_device(Gr);
+            h->err = "group emission: out of device memory at this window size (about 6 177 bytes per window wire: pass a smaller window_wires)";
+            return POB_E_NOMEM;
+        }
+        Gr.alloc_wires = window_wires;
+    }
+    if (lanes) { int rc = emit_probe_pass(h, group, window_wires, nwin_); if (rc) return rc; }
+    Gr.on = true; Gr.group = group; Gr.lanes = lanes; Gr.nsel = (uint32_t)__builtin_popcountll(lanes); Gr.next_bulk = 0;
+    *lanes_out = lanes;
+    E.win_wires = window_wires; E.nwin = lanes ? nwin_ : 0; E.idx = group * 64; E.next_make = 0; E.next_take = 0; E.first_slot = 0; E.active = true;
+    for (int k = 0; k < 2; k++) HIPC(hipEventRecord(Gr.ev_free[k], E.s_copy));
+    if (E.nwin) { int rc = group_make_window(h, 0); if (rc) return rc; E.next_make = 1; }
+    return POB_OK;
+}
+
+int pob_emit_next_group_packed(pob_handle h, const uint8_t* data[64], uint64_t bytes[64], uint64_t* first_wire, uint64_t* n_wires) {
+    if (!h || !data || !bytes || !first_wire || !n_wires) return POB_E_ARG;
+    pob_ctx::Emit& E = h->em; pob_ctx::Emit::Group& Gr = E.grp;
+    if (!E.active) { h->err = "pob_emit_next_group_packed without pob_emit_begin_group_packed"; return POB_E_STATE; }
+    if (!Gr.on) { h->err = "pob_emit_next_group_packed: the emission was not begun with pob_emit_begin_group_packed"; return POB_E_STATE; }
+    for (int l = 0; l < 64; l++) { data[l] = nullptr; bytes[l] = 0; }
+    if (E.next_take == E.nwin) { E.active = false; *first_wire = E.nwin ? E.total : 0; *n_wires = 0; return POB_OK; }
+    HIPC(hipSetDevice(h->device));
+    const uint64_t k = E.next_take;
+    // the window handed out by the previous call is released now.  Window k + 1's headers have crossed (or are about to): its copies are queued behind window k's, and with
+    // them in the queue its packed slot's successor, window k + 2, can be expanded -- k + 2 is expanded while k + 1 is copied and k is with the caller
+    while (Gr.next_bulk < E.next_make && Gr.next_bulk <= k + 1) { int rc = group_copy_window(h, Gr.next_bulk); if (rc) return rc; Gr.next_bulk++; }
+    while (E.next_make < E.nwin && E.next_make <= k + 2) {
+        if (Gr.next_bulk + 2 <= E.next_make) break;                         // (the packed slot's previous window has no copies queued yet)
+        int rc = group_make_window(h, E.next_make); if (rc) return rc;
+        E.next_make++;
+    }
+    E.next_take++;
+    const int hs = (int)(k % 3);
+    HIPC(hipEventSynchronize(Gr.ev_copied[hs]));
+    for (int l = 0; l < 64; l++) if (Gr.len[hs][l]) { data[l] = Gr.h_pin[hs] + Gr.off[hs][l]; bytes[l] = Gr.len[hs][l]; }
+    *first_wire = k * E.win_wires; *n_wires = std::min(E.win_wires, E.total - k * E.win_wires);
+    return POB_OK;
 }
 
 int pob_emit_selfcheck(pob_handle h, int enable) {
@@ -1805,6 +2035,78 @@ int pob_write_wtns_packed(pob_handle h, uint32_t idx, const uint32_t* keep, uint
     if (!h || !path) return POB_E_ARG;
     int rc = pob_emit_begin_packed(h, idx, keep, n_keep, 0);
     return rc ? rc : write_wtns_stream(h, path);
+}
+
+// the .wtns files of every selected witness of a group: one group emission, each witness' windows expanded on the host (pob_unpack_window) into its own file
+int pob_write_wtns_group(pob_handle h, uint32_t group, uint64_t lanes, const uint32_t* keep, uint64_t n_keep, const char* const paths[64]) {
+    if (!h || !paths) return POB_E_ARG;
+    uint64_t sel = 0;
+    int rc = pob_emit_begin_group_packed(h, group, lanes, keep, n_keep, 0, &sel);
+    if (rc) return rc;
+    for (int l = 0; l < 64; l++) if (((sel >> l) & 1) && !paths[l]) { h->em.active = false; return POB_E_ARG; }
+    const uint64_t W = h->em.total;
+    FILE* f[64]; bool ok = true;
+    for (int l = 0; l < 64; l++) f[l] = nullptr;
+    uint8_t* canon = (uint8_t*)malloc(std::max<uint64_t>(h->em.win_wires, 1) * 32);
+    auto fail = [&](int code, const std::string& msg) { for (int l = 0; l < 64; l++) if (f[l]) { fclose(f[l]); remove(paths[l]); } free(canon); h->em.active = false; if (!msg.empty()) h->err = msg; return code; };
+    if (!canon) return fail(POB_E_NOMEM, "out of host memory");
+    uint8_t hdr[76];
+    const uint64_t P64[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+    uint32_t u32; uint64_t u64v;
+    memcpy(hdr, "wtns", 4); u32 = 2; memcpy(hdr + 4, &u32, 4); memcpy(hdr + 8, &u32, 4);
+    u32 = 1; memcpy(hdr + 12, &u32, 4); u64v = 40; memcpy(hdr + 16, &u64v, 8);
+    u32 = 32; memcpy(hdr + 24, &u32, 4); memcpy(hdr + 28, P64, 32); u32 = (uint32_t)W; memcpy(hdr + 60, &u32, 4);
+    u32 = 2; memcpy(hdr + 64, &u32, 4); u64v = W * 32; memcpy(hdr + 68, &u64v, 8);
+    for (int l = 0; l < 64; l++) if ((sel >> l) & 1) {
+        if (!(f[l] = fopen(paths[l], "wb"))) return fail(POB_E_IO, std::string("cannot open ") + paths[l]);
+        ok = ok && fwrite(hdr, 1, 76, f[l]) == 76;
+    }
+    for (;;) {
+        const uint8_t* p[64]; uint64_t pb[64], w0, wn;
+        rc = pob_emit_next_group_packed(h, p, pb, &w0, &wn);
+        if (rc) return fail(rc, "");
+        if (!wn) break;
+        for (int l = 0; l < 64; l++) if (p[l]) {
+            if (pob_unpack_window(p[l], pb[l], canon, wn * 32, 0)) return fail(POB_E_STATE, "internal: a packed window does not validate");
+            ok = ok && fwrite(canon, 1, wn * 32, f[l]) == wn * 32;
+        }
+    }
+    for (int l = 0; l < 64; l++) if (f[l]) { ok = (fclose(f[l]) == 0) && ok; f[l] = nullptr; }
+    free(canon);
+    if (!ok) { for (int l = 0; l < 64; l++) if ((sel >> l) & 1) remove(paths[l]); h->err = "write failed"; return POB_E_IO; }
+    return POB_OK;
+}
+
+// pob_emit_measure_packed per group: `count` groups from first_group, each with the mask `lanes` (0: every good witness); pass 1 takes the windows as they arrive in pinned memory,
+// pass 2 also expands every witness' window into dst (one window's worth is enough); d2h_bytes = what pass 1 copied device-to-host
+int pob_emit_measure_group(pob_handle h, uint32_t first_group, uint32_t count, uint64_t lanes, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
+                           double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes) {
+    if (!h || !seconds_pinned || !d2h_bytes || count == 0 || threads < 0 || (dst && !seconds_expanded)) return POB_E_ARG;
+    HIPC(hipSetDevice(h->device));
+    for (int pass = 0; pass < (dst ? 2 : 1); pass++) {
+        const uint64_t d0 = h->em.pk_d2h; volatile uint8_t sink = 0;
+        timespec t0, t1; clock_gettime(CLOCK_MONOTONIC, &t0);
+        for (uint32_t i = 0; i < count; i++) {
+            uint64_t sel = 0;
+            int rc = pob_emit_begin_group_packed(h, first_group + i, lanes, keep, n_keep, window_wires, &sel);
+            if (rc) return rc;
+            if (pass && dst_cap < h->em.win_wires * 32) { h->em.active = false; h->err = "destination smaller than a window"; return POB_E_ARG; }
+            for (;;) {
+                const uint8_t* p[64]; uint64_t pb[64], w0, wn;
+                rc = pob_emit_next_group_packed(h, p, pb, &w0, &wn);
+                if (rc) return rc;
+                if (!wn) break;
+                for (int l = 0; l < 64; l++) if (p[l]) {
+                    sink = sink ^ p[l][0] ^ p[l][pb[l] - 1];
+                    if (pass) { rc = pob_unpack_window(p[l], pb[l], dst, wn * 32, threads); if (rc) { h->em.active = false; h->err = "internal: a packed window does not validate"; return rc; } }
+                }
+            }
+        }
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const double sec = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+        if (pass) *seconds_expanded = sec; else { *seconds_pinned = sec; *d2h_bytes = h->em.pk_d2h - d0; }
+    }
+    return POB_OK;
 }
 
 // emission throughput: K witnesses back to back through the window pipeline, the windows only touched (first + last cache line).

@@ -44,7 +44,7 @@
 //   CheckP  (device) re-reads every wire and verifies it against its defining expression evaluated
 //                    on the STORED operands (and every ===)                   -> constraint evaluator;
 //   EmitP   (device) re-reads every wire and writes it as a canonical 32-byte LE field element
-//                    at its O0 wire index                                     -> .wtns emitter.
+//                    at its O0 wire index                                     -> .wtns emitter (EmitPT<false>: one witness of the group, EmitPT<true>: all of them).
 #pragma once
 #include <stdint.h>
 #include "fr_dev.hpp"
@@ -550,9 +550,13 @@ struct CheckP : DevPol {
     __device__ __forceinline__ void run_flush() { run_resolve(); pend_s = pend_x = 0; }
 };
 
-// .wtns emitter for ONE witness of the group (lane `sel`): canonical 32-byte LE value at wire index.
-struct EmitP : DevPol {
-    static constexpr bool is_gen = false, is_check = false, is_emit = true, is_count = false, ride = false;
+// .wtns emitter: canonical 32-byte LE value at wire index.  GROUP = false: ONE witness of the group (lane `sel`).  GROUP = true (group emission, pob_emit_begin_group_packed): every
+// selected witness of the group at once -- lane l writes ITS witness' value into its own canonical window, out + l * plane; wherever the single-witness emitter singles out `sel`
+// (mine(), put(BitRef), run_w, circuits.hpp U_SC_RANGE) every lane of `lanes` acts.  The probe and site-recording passes are the single-witness kernels' (they do not depend on the witness).
+template <bool GROUP> struct EmitGroupState {};        // (nothing in the single-witness emitter: its policy object is what it was)
+template <> struct EmitGroupState<true> { uint64_t plane, lanes; };     // bytes between two witnesses' windows; bit l = witness l is emitted
+template <bool GROUP> struct EmitPT : DevPol, EmitGroupState<GROUP> {
+    static constexpr bool is_gen = false, is_check = false, is_emit = true, is_count = false, ride = false, is_group = GROUP;
     uint8_t* out;      // canonical witness payload of the wires [w0, w0 + wn) (the emission window), 32 B per wire
     uint32_t sel, w0, wn, unit;
     unsigned long long* probe;      // probe pass (once per window size): which windows does this unit write to?  bit w / wn of probe[unit]
@@ -569,13 +573,31 @@ struct EmitP : DevPol {
     // between a derived wire and a STORED one (an IsEqual child's outputs === the parent's stored isEq[] bit) a pair behind those.  sites[0..2] = the three counts.
     // path: 0..3 = the inverse path counted, | 4 = IsEqual parent.
     uint32_t* sites; uint32_t sites_cap;
+    __device__ __forceinline__ bool mine() const { if constexpr (GROUP) return (this->lanes >> m.lane) & 1; else return m.lane == sel; }      // does this lane write its witness' value?
     __device__ __forceinline__ void site_m(uint32_t w_next, uint32_t w_byte, uint32_t k) {      // M[k+1] (wire w_next) === M[k] (w_next - 1) + mainInput[k] (w_byte) * 256^k
-        if (sites && m.lane == sel) { const uint32_t i = atomicAdd(sites + 1, 1u); if (i < sites_cap) { uint32_t* q = sites + 4 + sites_cap + 3 * (size_t)i; q[0] = w_next; q[1] = w_byte; q[2] = k; } }
+        if constexpr (!GROUP) { if (sites && m.lane == sel) { const uint32_t i = atomicAdd(sites + 1, 1u); if (i < sites_cap) { uint32_t* q = sites + 4 + sites_cap + 3 * (size_t)i; q[0] = w_next; q[1] = w_byte; q[2] = k; } } }
     }
     __device__ __forceinline__ void site_c(uint32_t w, uint32_t src) {              // wire w === wire src  (one lane calls)
-        if (sites) { const uint32_t i = atomicAdd(sites + 2, 1u); if (i < sites_cap) { uint32_t* q = sites + 4 + 4 * (size_t)sites_cap + 2 * (size_t)i; q[0] = w > src ? w : src; q[1] = w > src ? src : w; } }
+        if constexpr (!GROUP) { if (sites) { const uint32_t i = atomicAdd(sites + 2, 1u); if (i < sites_cap) { uint32_t* q = sites + 4 + 4 * (size_t)sites_cap + 2 * (size_t)i; q[0] = w > src ? w : src; q[1] = w > src ? src : w; } } }
+    }
+    // GROUP: wire w -> its position in the window (reduced: its rank among the kept wires); false = dropped, or outside the window
+    __device__ __forceinline__ bool locate(uint32_t& w) const {
+        if (rbits) {
+            const unsigned long long word = rbits[w >> 6];
+            if (!((word >> (w & 63)) & 1)) return false;
+            w = rpre[w >> 6] + (uint32_t)__popcll(word & ((1ull << (w & 63)) - 1));
+        }
+        w -= w0;
+        return w < wn;
     }
     __device__ __forceinline__ void w32(uint32_t w, const F& canon, int path = -1) {
+        if constexpr (GROUP) {
+            if (!locate(w)) return;              // (the path counters of pob_debug_emit_counters count the single-witness emitter's wires only: not touched here)
+            uint4* q = (uint4*)(out + (size_t)m.lane * this->plane + (size_t)w * 32);
+            q[0] = make_uint4(canon.l[0], canon.l[1], canon.l[2], canon.l[3]);
+            q[1] = make_uint4(canon.l[4], canon.l[5], canon.l[6], canon.l[7]);
+            return;
+        }
         if (sites) { if (path >= 0) { const uint32_t i = atomicAdd(sites, 1u); if (i < sites_cap) sites[4 + i] = (w - 2) | ((path & 4) ? 0x80000000u : 0u); } return; }
         if (rbits) {
             const unsigned long long word = rbits[w >> 6];
@@ -589,25 +611,39 @@ struct EmitP : DevPol {
         q[0] = make_uint4(canon.l[0], canon.l[1], canon.l[2], canon.l[3]);
         q[1] = make_uint4(canon.l[4], canon.l[5], canon.l[6], canon.l[7]);
     }
+    // GROUP: this lane's wire w carries the 64-witness mask x: bit l goes into witness l's window, for every selected l (a run of consecutive wires is one contiguous
+    // 2 KB piece per witness)
+    __device__ __forceinline__ void run_w(bool active, uint32_t w, B x) {
+        if constexpr (GROUP) {
+            if (!(active && locate(w))) return;
+            uint8_t* q = out + (size_t)w * 32;
+            for (uint64_t ls = this->lanes; ls; ls &= ls - 1) {
+                const uint32_t l = (uint32_t)__builtin_ctzll(ls);
+                uint4* d = (uint4*)(q + (size_t)l * this->plane); d[0] = make_uint4((uint32_t)((x >> l) & 1), 0, 0, 0); d[1] = make_uint4(0, 0, 0, 0);
+            }
+        }
+    }
     __device__ __forceinline__ F small(S k) {
         Fr c = {{(uint32_t)(k < 0 ? -k : k), 0, 0, 0, 0, 0, 0, 0}};
         return (k < 0) ? fr_sub(fr_zero(), c) : c;     // canonical arithmetic: p - |k|
     }
     __device__ __forceinline__ B put(BitRef r, B) {
         B s = ld(r);
-        if (m.lane == 0) { Fr c = {{(uint32_t)((s >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(r.w, c); }
+        if constexpr (GROUP) { if (mine()) { Fr c = {{(uint32_t)((s >> m.lane) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(r.w, c); } }
+        else if (m.lane == 0) { Fr c = {{(uint32_t)((s >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(r.w, c); }
         return s;
     }
-    __device__ __forceinline__ S put(SmRef r, S) { S s = ld(r); if (m.lane == sel) w32(r.w, small(s)); return s; }
-    __device__ __forceinline__ F put(FrRef r, const F&) { F s = ld(r); if (m.lane == sel) w32(r.w, fr_from_mont(s)); return s; }
+    __device__ __forceinline__ S put(SmRef r, S) { S s = ld(r); if (mine()) w32(r.w, small(s)); return s; }
+    __device__ __forceinline__ F put(FrRef r, const F&) { F s = ld(r); if (mine()) w32(r.w, fr_from_mont(s)); return s; }
     __device__ __forceinline__ B hint(BitRef r, B v) { return put(r, v); }
     __device__ __forceinline__ S hint(SmRef r, S v) { return put(r, v); }
     __device__ __forceinline__ F hint(FrRef r, const F& v) { return put(r, v); }
-    __device__ __forceinline__ void derived(uint32_t w, S v) { if (m.lane == sel) w32(w, small(v)); }          // (shadow DevPol's no-ops)
+    __device__ __forceinline__ void derived(uint32_t w, S v) { if (mine()) w32(w, small(v)); }          // (shadow DevPol's no-ops)
     __device__ __forceinline__ void derived_inv(uint32_t w, S x, bool iseq = false) { emit_inv(w, x, iseq); }
-    __device__ __forceinline__ void derived_fr(uint32_t w, const F& v) { if (m.lane == sel) w32(w, fr_from_mont(v)); }
-    __device__ __forceinline__ void derived_fr_inv(uint32_t w, const F& x, bool iseq = true) { if (m.lane == sel) { const bool z = fr_is_zero(x); w32(w, z ? fr_zero() : fr_from_mont(fr_inv(x)), (z ? 3 : 2) | (iseq ? 4 : 0)); } }       // (iseq: an IsEqual's child, gadgets.hpp iseqf_derived; false: a bare IsZero, gIsZeroFd)
-    // the selected witness' value in every lane (a unit that has many inverses to rebuild spreads them over the lanes: circuits.hpp U_SC_RANGE)
+    __device__ __forceinline__ void derived_fr(uint32_t w, const F& v) { if (mine()) w32(w, fr_from_mont(v)); }
+    __device__ __forceinline__ void derived_fr_inv(uint32_t w, const F& x, bool iseq = true) { if (mine()) { const bool z = fr_is_zero(x); w32(w, z ? fr_zero() : fr_from_mont(fr_inv(x)), (z ? 3 : 2) | (iseq ? 4 : 0)); } }       // (iseq: an IsEqual's child, gadgets.hpp iseqf_derived; false: a bare IsZero, gIsZeroFd)
+    // the selected witness' value in every lane (a unit that has many inverses to rebuild spreads them over the lanes: circuits.hpp U_SC_RANGE; the group emitter
+    // has 64 witnesses' inverses to rebuild and every lane inverts its own)
     __device__ __forceinline__ F bcast_sel(const F& v) {
         F r;
 #pragma unroll
@@ -615,7 +651,7 @@ struct EmitP : DevPol {
         return r;
     }
     __device__ __forceinline__ void emit_inv(uint32_t w, S k, bool iseq = false) {
-        if (m.lane == sel) {
+        if (mine()) {
             F c;
             if (k >= -4096 && k <= 4096) {
                 const uint32_t* q = m.inv_lut + (size_t)(k + 4096) * 8;
@@ -631,11 +667,17 @@ struct EmitP : DevPol {
     __device__ __forceinline__ void require(B, uint32_t) {}
     __device__ __forceinline__ void require_lane(bool, uint32_t) {}
     // derived BIT wires: lane k < n writes wire w (its own) from the mask x it holds
-    __device__ __forceinline__ void run_derived(uint32_t n, uint32_t w, B x) { if (m.lane < n) { Fr c = {{(uint32_t)((x >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(w, c); } }
+    __device__ __forceinline__ void run_derived(uint32_t n, uint32_t w, B x) {
+        if constexpr (GROUP) run_w(m.lane < n, w, x);
+        else if (m.lane < n) { Fr c = {{(uint32_t)((x >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(w, c); }
+    }
     __device__ __forceinline__ void run_put(uint32_t n, uint32_t w, uint32_t i, B) {
-        if (m.lane < n) { B s = run_ld_off(i << 3); Fr c = {{(uint32_t)((s >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(w, c); }
+        if constexpr (GROUP) run_w(m.lane < n, w, run_ld_off(run_off(n, i)));
+        else if (m.lane < n) { B s = run_ld_off(i << 3); Fr c = {{(uint32_t)((s >> sel) & 1), 0, 0, 0, 0, 0, 0, 0}}; w32(w, c); }
     }
 };
+typedef EmitPT<false> EmitP;
+typedef EmitPT<true> EmitGroupP;
 
 // Gadget-level mains (gadget_mains.hpp: the reference's test wrappers around single templates, tests/test.py:146-201): the main component
 // IS the template, so its SM input arrays are not wires of a parent but the packed inputs.  A reference with w >= GM_INPUT_W stands for

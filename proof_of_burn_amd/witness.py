@@ -188,6 +188,12 @@ def load_library() -> ctypes.CDLL:
         lib.pob_write_wtns_packed.argtypes = [vp, ctypes.c_uint32, vp, ctypes.c_uint64, ctypes.c_char_p]
         lib.pob_emit_measure_packed.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(lib, "pob_emit_begin_group_packed"):      # (absent in an older build named by POB_LIB_PATH: tools/emit_rate.py --parent)
+        lib.pob_emit_begin_group_packed.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        lib.pob_emit_next_group_packed.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        lib.pob_write_wtns_group.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p)]
+        lib.pob_emit_measure_group.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
     lib.pob_time_kernel.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
     lib.pob_probe_check_kernel.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     lib.pob_debug_xor_bits.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
@@ -215,7 +221,7 @@ EXPORTED_SYMBOLS = ["pob_plan_info", "pob_gadget_template", "pob_open", "pob_clo
                     "pob_upload_inputs8", "pob_upload_inputs8_async", "pob_narrow_inputs", "pob_pack_json_batch8",
                     "pob_results_fetch", "pob_results_wait", "pob_emit_begin_reduced", "pob_reduced_map_pin", "pob_write_wtns_reduced", "pob_emit_measure_ex", "pob_generate",
                     "pob_constraint_check", "pob_sync", "pob_set_partner", "pob_results", "pob_results_device", "pob_results_records_device", "pob_gather_records", "pob_emit_witness",
-                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
+                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
 
 
 def plan_info(main: str) -> PobInfo:
@@ -855,6 +861,71 @@ class WitnessCalculator:
         self._ck(self.lib.pob_emit_measure_packed(self.h, first_idx, count, window_wires, k.ctypes.data if k is not None else None, k.size if k is not None else 0,
                                                   out.ctypes.data if out is not None else None, out.nbytes if out is not None else 0, threads,
                                                   ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(nb)))
+        return s0.value, (s1.value if out is not None else None), nb.value
+
+    # ---- group emission (pob_emit_begin_group_packed): the packed windows of every selected witness of one group of 64 from a single pass over the resident vector
+    @staticmethod
+    def _lane_mask(lanes) -> int:
+        """None / 0: every good witness of the group; an int mask (bit l = witness 64 * group + l) or an iterable of lane numbers"""
+        if lanes is None:
+            return 0
+        if isinstance(lanes, (int, np.integer)):
+            return int(lanes)
+        m = 0
+        for l in lanes:
+            if not 0 <= int(l) < 64:
+                raise ValueError("lanes: lane numbers 0..63")
+            m |= 1 << int(l)
+        if m == 0:
+            raise ValueError("lanes: an empty selection (None selects every good witness of the group)")
+        return m
+
+    def group_packed_windows(self, group: int, window_wires: int = 0, keep=None, lanes=None):
+        """stream the witnesses 64 * group .. + 63 as packed windows: yields (first_wire, n_wires, {lane: uint8 view of that witness' packed window}) per window -- each view byte
+        for byte what packed_windows(64 * group + lane, window_wires, keep) yields; the views are valid until the next iteration (they alias the handle's pinned buffers).
+        lanes: None = every witness of the group that is in the batch and passed its asserts (a failed one is simply absent from the dict), else a mask or lane numbers (a failed
+        or missing witness named there raises).  window_wires = 0: 4 Mi positions"""
+        k = None if keep is None else self._keep_array(keep)
+        used = ctypes.c_uint64()
+        self._ck(self.lib.pob_emit_begin_group_packed(self.h, group, self._lane_mask(lanes), k.ctypes.data if k is not None else None, k.size if k is not None else 0, window_wires,
+                                                      ctypes.byref(used)))
+        self.group_lanes = int(used.value)               # the mask the library used (lanes=None: which witnesses are being emitted)
+        p, nb, w0, wn = (ctypes.c_void_p * 64)(), (ctypes.c_uint64 * 64)(), ctypes.c_uint64(), ctypes.c_uint64()
+        while True:
+            self._ck(self.lib.pob_emit_next_group_packed(self.h, p, nb, ctypes.byref(w0), ctypes.byref(wn)))
+            if wn.value == 0:
+                return
+            yield w0.value, wn.value, {l: np.frombuffer((ctypes.c_uint8 * nb[l]).from_address(p[l]), dtype=np.uint8) for l in range(64) if p[l]}
+
+    def write_wtns_group(self, group: int, paths, keep=None, lanes=None) -> int:
+        """the .wtns files of the group's selected witnesses from one group emission, each byte for byte write_wtns / write_wtns_reduced of that witness (pob_write_wtns_group).
+        paths: {lane: path} or a sequence indexed by lane (entries of unselected lanes are ignored); -> the mask of the lanes written"""
+        k = None if keep is None else self._keep_array(keep)
+        arr = (ctypes.c_char_p * 64)()
+        items = paths.items() if isinstance(paths, dict) else enumerate(paths)
+        for l, pth in items:
+            if pth is not None:
+                arr[int(l)] = os.fsencode(pth)
+        mask = self._lane_mask(lanes)
+        if mask == 0:                                    # which lanes will be written: the rule of pob_emit_begin_group_packed's lanes = 0 (include/pob_hip.h) -- in the batch and generation
+                                                         # status 0, which is what Result.ok says -- restated here because the C call has no lanes_out; keep the two in step
+            st = self.results()
+            mask = sum(1 << l for l in range(64) if 64 * group + l < len(st) and st[64 * group + l].ok)
+        if any((mask >> l) & 1 and not arr[l] for l in range(64)):
+            raise ValueError("write_wtns_group: no path for a selected lane")
+        self._ck(self.lib.pob_write_wtns_group(self.h, group, mask, k.ctypes.data if k is not None else None, k.size if k is not None else 0, arr))
+        return mask
+
+    def emit_throughput_group(self, first_group: int = 0, count: int = 1, window_wires: int = 0, keep=None, lanes=None, out: np.ndarray | None = None, threads: int = 0):
+        """(seconds until the packed windows of every selected witness of `count` groups are in pinned memory, seconds with the host expansion of every window into `out` included
+        -- None without `out` --, bytes copied device-to-host).  out: uint8, at least one window of 32-byte values (pob_emit_measure_group)"""
+        s0, s1, nb = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
+        k = None if keep is None else self._keep_array(keep)
+        if out is not None and (out.dtype != np.uint8 or not out.flags.c_contiguous):
+            raise ValueError("out: a contiguous uint8 array")
+        self._ck(self.lib.pob_emit_measure_group(self.h, first_group, count, self._lane_mask(lanes), window_wires, k.ctypes.data if k is not None else None, k.size if k is not None else 0,
+                                                 out.ctypes.data if out is not None else None, out.nbytes if out is not None else 0, threads,
+                                                 ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(nb)))
         return s0.value, (s1.value if out is not None else None), nb.value
 
     def time_kernel(self, which: int, iters: int = 5, stream: int | None = None) -> float:

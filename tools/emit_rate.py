@@ -4,7 +4,11 @@
     python tools/emit_rate.py --packed [--pairs N] [--parent LIB]
         the packed transfer (pob_emit_measure_packed) beside the canonical one.  --parent: another build of the library (the parent commit's) measured in a second
         process that takes turns with this one, pair by pair, on the same GPU: its canonical figures are the baseline.  Prints medians and ranges.
-    python tools/emit_rate.py --trace-one                ONE packed O0 production emission and nothing else after the generation (for rocprofv3 --kernel-trace --stats)"""
+    python tools/emit_rate.py --group [--pairs N] [--parent LIB]
+        the group emission (pob_emit_measure_group: all 64 witnesses of the group in one pass) beside the single-witness packed path -- of the parent's library with
+        --parent, else of this one -- taking turns; per form: ms per witness into pinned memory, with the host expansion, and D2H bytes per witness.
+    python tools/emit_rate.py --trace-one [--group]      ONE packed O0 production emission (--group: one group emission) and nothing else after the generation (for
+                                                         rocprofv3 --kernel-trace --stats)"""
 import json
 import os
 import statistics
@@ -68,6 +72,15 @@ def serve():
             p1, e1, d1 = calc.emit_throughput_packed(1, 6, RED_WIN, keep=keep, out=buf)
             print(json.dumps({"o0_pinned_ms": p0 / 3 * 1e3, "o0_expanded_ms": e0 / 3 * 1e3, "o0_d2h": d0 // 3,
                               "red_pinned_ms": p1 / 6 * 1e3, "red_expanded_ms": e1 / 6 * 1e3, "red_d2h": d1 // 6}), flush=True)
+        elif cmd == "group":
+            if buf is None:
+                buf = np.zeros(32 * RED_WIN, dtype=np.uint8)
+            if cmd not in warm:
+                calc.emit_throughput_group(0, 1, 0, out=buf); calc.emit_throughput_group(0, 1, 0, keep=keep, out=buf); warm.add(cmd)
+            p0, e0, d0 = calc.emit_throughput_group(0, 1, 0, out=buf)
+            p1, e1, d1 = calc.emit_throughput_group(0, 1, 0, keep=keep, out=buf)
+            print(json.dumps({"o0_pinned_ms": p0 / 64 * 1e3, "o0_expanded_ms": e0 / 64 * 1e3, "o0_d2h": d0 // 64,
+                              "red_pinned_ms": p1 / 64 * 1e3, "red_expanded_ms": e1 / 64 * 1e3, "red_d2h": d1 // 64}), flush=True)
         elif cmd == "unpack":
             from proof_of_burn_amd import witness as W
             if buf is None:
@@ -140,7 +153,35 @@ def packed(pairs, parent):
         print(f"  {k}: {v['wires']} wires, {v['packed_bytes']} B packed -> {v['ms']:.2f} ms, {v['canonical_GBps']:.1f} GB/s of canonical bytes written")
 
 
+def group(pairs, parent):
+    new = Proc()
+    old = Proc(parent) if parent else new
+    rows = {"single": [], "group": []}
+    try:
+        old.ask("packed"); new.ask("group")                           # warm-up: allocations and probe passes
+        for _ in range(pairs):                                        # the two paths take turns on one GPU
+            rows["single"].append(old.ask("packed"))
+            rows["group"].append(new.ask("group"))
+    finally:
+        for who in {old, new}:
+            who.close()
+    print(f"{MAIN}, one calculator, 64 witnesses resident; per witness; {pairs} rounds, the two paths taking turns on one GPU")
+    for form, key in (("O0 (215 907 954 wires)", "o0"), ("reduced (21 454 032 kept wires)", "red")):
+        print(f"{form}:")
+        for name, who in ((("parent library" if parent else "this library") + ", single-witness packed path", "single"), ("this library, group emission of 64            ", "group")):
+            r = rows[who]
+            print(f"  {name}: into pinned memory {_fmt([x[key + '_pinned_ms'] for x in r])}; with the host expansion {_fmt([x[key + '_expanded_ms'] for x in r])}; {r[0][key + '_d2h']} B D2H")
+        a, b = statistics.median(x[key + "_pinned_ms"] for x in rows["single"]), statistics.median(x[key + "_pinned_ms"] for x in rows["group"])
+        print(f"  witnesses per second, group / single: {a / b:.1f} x")
+
+
 def trace_one():
+    if "--group" in sys.argv:
+        calc, _ = open_calc()
+        sec, _, d2h = calc.emit_throughput_group(0, 1, 0)
+        print(f"one O0 group emission of 64 (first of the handle: allocation and probe pass included): {sec * 1e3:.1f} ms, {d2h} B D2H")
+        calc.close()
+        return
     calc, _ = open_calc()
     sec, _, d2h = calc.emit_throughput_packed(1, 1, 0)
     print(f"one packed O0 emission (first of the handle: allocation and probe pass included): {sec * 1e3:.1f} ms, {d2h} B D2H")
@@ -153,6 +194,8 @@ if __name__ == "__main__":
         serve()
     elif "--trace-one" in a:
         trace_one()
+    elif "--group" in a:
+        group(int(a[a.index("--pairs") + 1]) if "--pairs" in a else 7, a[a.index("--parent") + 1] if "--parent" in a else None)
     elif "--packed" in a:
         packed(int(a[a.index("--pairs") + 1]) if "--pairs" in a else 5, a[a.index("--parent") + 1] if "--parent" in a else None)
     else:
