@@ -303,7 +303,7 @@ int pob_emit_measure_packed(pob_handle h, uint32_t first_idx, uint32_t count, ui
  *                   pinned   3 slots, each nsel * fixed(w) + the value sections as the nsel headers count them (+ 1/8), grown on demand: ~ 0.26 bytes per wire, witness and slot for an
  *                            O0 payload -- never 64 canonical windows
  *                 POB_E_NOMEM where either allocation fails (nothing of the emission is kept; a smaller window_wires needs proportionally less).
- *   POB_E_STATE while pob_emit_selfcheck is on: the self-check of group emissions is not implemented (out of scope), switch it off first; and on a handle opened on a
+ *   POB_E_STATE while pob_emit_selfcheck is on: the single-witness switch does not cover group emissions, use pob_emit_group_selfcheck (below); and on a handle opened on a
  *   gadget-level main (pob_gadget_template), which has no group emitter.  An empty mask allocates nothing.  pob_debug_emit_counters counts the single-witness emitter's wires
  *   only: a group emission leaves the counters as they are.
  * pob_emit_next_group_packed: data[l] / bytes[l] = witness l's complete packed window in pinned memory owned by the handle, valid until the following call; NULL / 0 for an
@@ -320,6 +320,17 @@ int pob_write_wtns_group(pob_handle h, uint32_t group, uint64_t lanes, const uin
  * that also expands every witness' every window into dst gives *seconds_expanded. */
 int pob_emit_measure_group(pob_handle h, uint32_t first_group, uint32_t count, uint64_t lanes, uint64_t window_wires, const uint32_t* keep, uint64_t n_keep, uint8_t* dst, uint64_t dst_cap, int threads,
                            double* seconds_pinned, double* seconds_expanded, uint64_t* d2h_bytes);
+/* SELF-CHECK OF GROUP EMISSIONS.  A switch of its own: enable = 1 makes every following group emission (pob_emit_begin_group_packed, pob_write_wtns_group,
+ * pob_emit_measure_group) evaluate the relations listed at pob_emit_selfcheck on the values the group emitter wrote for EVERY selected witness, each witness on its own window of
+ * the group's canonical scratch, behind the window's last writer and in front of the pack pass: still one pass, one verdict per witness.  The check only reads: the packed windows
+ * are byte for byte those of an unchecked group emission.  The site tables are the handle's (the first checked emission of either kind records them); the reduced form uses the
+ * lists of pob_emit_selfcheck's reduced form, and pob_emit_selfcheck_alias serves both switches.  None of the three entry points fails on a violation: read the result afterwards.
+ * pob_emit_group_selfcheck_result: *lanes = the mask that was emitted; *checked / *skipped = relations evaluated / skipped PER WITNESS, with the meaning of
+ * pob_emit_selfcheck_result (they depend on positions only: the same for every selected witness); first_bad_wire[l] = the lowest wire of witness 64 * group + l whose relation
+ * does not hold, 0xFFFFFFFF for a clean or unselected lane.  The result is that of the last checked group emission that was read to its END (pob_emit_next_group_packed returned
+ * n_wires = 0); POB_E_STATE before any, and from the begin of a checked group emission until its end -- windows are made ahead of the caller -- also when it is abandoned. */
+int pob_emit_group_selfcheck(pob_handle h, int enable);
+int pob_emit_group_selfcheck_result(pob_handle h, uint64_t* lanes, uint64_t* checked, uint64_t* skipped, uint32_t first_bad_wire[64]);
 
 /* Measurement: average duration (ms, HIP events on `stream`) of `iters` back-to-back launches of one kernel over
  * the current batch.  which: 0 = Keccak round expansion (generate), 1 = Keccak round constraint evaluation,
@@ -351,6 +362,16 @@ void pob_debug_stream_destroy(int device, void* stream);
  * to corrupt: corrupting the stored wire they are a function / a copy of changes them with it.)                                    */
 enum { POB_CLASS_BIT = 0, POB_CLASS_SM = 1, POB_CLASS_FR = 2 };
 int pob_debug_poke(pob_handle h, int cls, uint32_t group, uint64_t index, uint32_t sub, uint32_t lane, uint32_t xor_mask);
+/* Test hook: the recorded O0 site tables of the self-checks as 32-bit words, sorted by wire -- kind 0: one word per IsZero [out | in | inv] = its first wire (bit 31: child of an
+ * IsEqual [out | in[2]] three wires below); kind 1: M triples {wire of M[k+1], wire of mainInput[k], k}; kind 2: copy pairs {higher wire, lower wire}.  *n = the number of words;
+ * out (may be NULL) receives them if cap >= *n.  Runs the recording pass if the tables are not built yet: needs a generated batch.  Kinds 3 / 4: the reduced form's lists as
+ * the last checked reduced emission (either switch) built them for its map and alias -- six wires per IsZero site / {M[k+1], M[k], mainInput[k], k} per M step, each wire
+ * through its class representative (bit 31: a small constant); POB_E_STATE before any such emission. */
+int pob_debug_selfcheck_sites(pob_handle h, int kind, uint32_t* out, uint64_t cap, uint64_t* n);
+/* Test hook for the group self-check: in the NEXT group emission only (at most 16 entries per emission), in the window that holds `wire` (O0 position, or rank among the kept
+ * wires), byte `byte` (0..31) of lane `lane`'s canonical value is XORed with `mask` after the expansion and before the check.  The corrupted byte also reaches that witness'
+ * packed window.  (A poke of the resident vector moves M[] and mainInput[] together; this reaches a single written value.) */
+int pob_debug_group_emit_xor(pob_handle h, uint32_t lane, uint32_t wire, uint32_t byte, uint8_t mask);
 /* Test hook: how many IsZero.inv wires the emitter has written since the last reset through each of its paths: out[0] from the table of small
  * inverses (|operand| <= 4096), out[1] by Fermat exponentiation (larger small operands), out[2] / out[3] field-element operands, non-zero
  * (Kaliski inversion) / zero.  Call when an emission is complete.                                                                     */

@@ -16,6 +16,7 @@
 #include "../../include/pob_hip.h"
 #include "kernels_common.hpp"
 #include "pack_window.hpp"
+#include "selfcheck.hpp"
 
 
 __global__ void k_init_invlut(uint32_t* lut) {   // canonical inverses of -4096..4096
@@ -173,90 +174,51 @@ __global__ void k_fr_sqr_test(const uint32_t* in, uint32_t* out_sqr, uint32_t* o
 // (reference: circomlib comparators.circom IsZero `out <== -in*inv + 1; in*out === 0`, IsEqual `in[1] - in[0] ==> isz.in; isz.out ==> out`;
 //  substring_check.circom:45-49 `M[i+1] <== M[i] + mainInput[i] * 256^i`).  One thread per site; sites whose wires are not all inside the window are counted as
 // skipped by the host (IsZero / IsEqual) or here (M).  res[0] = lowest violated wire, res[1] = M sites skipped.
-// where wire w lies in the window: O0 (rbits null) position w - w0; reduced witness: its rank among the kept wires - w0, false if the wire is dropped
-struct ScWin { const uint8_t* win; uint32_t w0, wn; const unsigned long long* rbits; const uint32_t* rpre; };
-__device__ __forceinline__ bool sc_pos(const ScWin& W, uint32_t w, uint32_t* pos) {
-    if (!W.rbits) { *pos = w - W.w0; return *pos < W.wn; }
-    const unsigned long long word = W.rbits[w >> 6];
-    if (!((word >> (w & 63)) & 1)) return false;
-    *pos = W.rpre[w >> 6] + (uint32_t)__popcll(word & ((1ull << (w & 63)) - 1)) - W.w0;
-    return *pos < W.wn;
-}
-__device__ __forceinline__ Fr sc_load(const ScWin& W, uint32_t pos) {
-    const uint32_t* q = (const uint32_t*)(W.win + (size_t)pos * 32);
-    Fr c; for (int j = 0; j < 8; j++) c.l[j] = q[j];
-    return fr_to_mont(c);
-}
+// (ScWin / sc_pos / sc_load and ONE statement of every relation: selfcheck.hpp, shared with the group kernels of k_selfcheck_group.hip)
 // (a site with a wire outside the window -- or, in the reduced witness, a dropped wire: the relation then lives between class representatives the keep map alone does
 //  not name -- is skipped and counted in res[1])
 __global__ void __launch_bounds__(64) k_selfcheck_z(ScWin W, const uint32_t* sites, uint32_t n, uint32_t* res) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint32_t s = sites[t], w = s & 0x7FFFFFFFu;                  // IsZero [out | in | inv] at w
-    uint32_t po, pi, pv, pe = 0, pa = 0, pb = 0;
-    bool have = sc_pos(W, w, &po) && sc_pos(W, w + 1, &pi) && sc_pos(W, w + 2, &pv);
-    if (have && (s >> 31)) have = sc_pos(W, w - 3, &pe) && sc_pos(W, w - 2, &pa) && sc_pos(W, w - 1, &pb);
-    if (!have) { atomicAdd(res + 1, 1u); return; }
-    const Fr out = sc_load(W, po), in = sc_load(W, pi), inv = sc_load(W, pv);
-    bool ok = fr_eq(fr_mul(in, inv), fr_sub(fr_one_mont(), out)) && fr_is_zero(fr_mul(in, out));
-    if (s >> 31) {                                                       // IsEqual [out | in[2]] at w - 3
-        const Fr eo = sc_load(W, pe), a = sc_load(W, pa), b = sc_load(W, pb);
-        ok = ok && fr_eq(in, fr_sub(b, a)) && fr_eq(eo, out);
-    }
-    if (!ok) atomicMin(res, w);
+    uint32_t w = 0;
+    const uint32_t r = sc_rel_z(W, sites[t], &w);                      // IsZero [out | in | inv] at w; bit 31: IsEqual [out | in[2]] at w - 3
+    if (r == SC_SKIP) atomicAdd(res + 1, 1u);
+    else if (r == SC_BAD) atomicMin(res, w);
 }
 // copy constraints a === b between a derived wire and the stored wire it must equal (pairs {higher wire, lower wire})
 __global__ void __launch_bounds__(64) k_selfcheck_c(ScWin W, const uint32_t* sites, uint32_t n, uint32_t* res) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint32_t a = sites[2 * t], b = sites[2 * t + 1];
-    uint32_t pa, pb;
-    if (!sc_pos(W, a, &pa) || !sc_pos(W, b, &pb)) { atomicAdd(res + 1, 1u); return; }      // (the lower wire lies in the window before, or one of the two is dropped)
-    const uint4* p = (const uint4*)(W.win + (size_t)pa * 32); const uint4* q = (const uint4*)(W.win + (size_t)pb * 32);
-    const uint4 x0 = p[0], x1 = p[1], y0 = q[0], y1 = q[1];
-    if (x0.x != y0.x || x0.y != y0.y || x0.z != y0.z || x0.w != y0.w || x1.x != y1.x || x1.y != y1.y || x1.z != y1.z || x1.w != y1.w) atomicMin(res, a);
+    uint32_t w = 0;
+    const uint32_t r = sc_rel_c(W, sites[2 * t], sites[2 * t + 1], &w);
+    if (r == SC_SKIP) atomicAdd(res + 1, 1u);
+    else if (r == SC_BAD) atomicMin(res, w);
 }
 __global__ void __launch_bounds__(64) k_selfcheck_m(ScWin W, const uint32_t* sites, uint32_t n, const uint32_t* pow256, uint32_t* res) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint32_t wn1 = sites[3 * t], wb = sites[3 * t + 1], k = sites[3 * t + 2];
-    uint32_t pn, pp, pby;
-    if (!sc_pos(W, wn1, &pn) || !sc_pos(W, wn1 - 1, &pp) || !sc_pos(W, wb, &pby)) { atomicAdd(res + 1, 1u); return; }
-    Fr pw; for (int j = 0; j < 8; j++) pw.l[j] = pow256[(size_t)k * 8 + j];                      // 256^k, Montgomery
-    const Fr next = sc_load(W, pn), prev = sc_load(W, pp), by = sc_load(W, pby);
-    if (!fr_eq(next, fr_add(prev, fr_mul(by, pw)))) atomicMin(res, wn1);
+    uint32_t w = 0;
+    const uint32_t r = sc_rel_m(W, sites[3 * t], sites[3 * t + 1], sites[3 * t + 2], pow256, &w);
+    if (r == SC_SKIP) atomicAdd(res + 1, 1u);
+    else if (r == SC_BAD) atomicMin(res, w);
 }
-// the same relations on explicit wire lists (reduced witness): every wire of a site is kept (the host left the others out); a site is evaluated in the window that holds
-// its first wire -- if the others lie there too (else skipped: res[1]); res[2] counts the sites evaluated
+// the same relations on explicit wire lists (reduced witness): a site is evaluated in the window that holds its first wire -- if the others lie there too (else
+// skipped: res[1]); res[2] counts the sites evaluated
 __global__ void __launch_bounds__(64) k_selfcheck_zr(ScWin W, const uint32_t* zw, uint32_t n, uint32_t* res) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint32_t* w6 = zw + 6 * (size_t)t;                            // IsZero out, in, inv | IsEqual out, in[0], in[1] (0xFFFFFFFF: a bare IsZero)
-    uint32_t p[6];                                                      // (an entry with bit 31 set: a wire pinned to the small constant in its low bits -- not in the window at all)
-    if (!sc_pos(W, w6[0], &p[0])) return;
-    const bool iseq = w6[3] != 0xFFFFFFFFu;
-    auto pos = [&](int j) { if (w6[j] >> 31) { p[j] = w6[j]; return true; } return sc_pos(W, w6[j], &p[j]); };
-    bool have = pos(1) && pos(2);
-    if (have && iseq) have = pos(3) && pos(4) && pos(5);
-    if (!have) { atomicAdd(res + 1, 1u); return; }
-    atomicAdd(res + 2, 1u);
-    auto val = [&](int j) { if (p[j] >> 31) { Fr c = fr_zero(); c.l[0] = p[j] & 0x7FFFFFFFu; return fr_to_mont(c); } return sc_load(W, p[j]); };
-    const Fr out = val(0), in = val(1), inv = val(2);
-    bool ok = fr_eq(fr_mul(in, inv), fr_sub(fr_one_mont(), out)) && fr_is_zero(fr_mul(in, out));
-    if (iseq) { const Fr eo = val(3), a = val(4), b = val(5); ok = ok && fr_eq(in, fr_sub(b, a)) && fr_eq(eo, out); }
-    if (!ok) atomicMin(res, w6[0]);
+    uint32_t w = 0;
+    const uint32_t r = sc_rel_zr(W, zw + 6 * (size_t)t, &w);
+    if (r == SC_SKIP) atomicAdd(res + 1, 1u);
+    else if (r != SC_NONE) { atomicAdd(res + 2, 1u); if (r == SC_BAD) atomicMin(res, w); }
 }
 __global__ void __launch_bounds__(64) k_selfcheck_mr(ScWin W, const uint32_t* mw, uint32_t n, const uint32_t* pow256, uint32_t* res) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const uint32_t* w4 = mw + 4 * (size_t)t;                            // M[k+1], M[k], mainInput[k], k
-    uint32_t pn, pp, pby;
-    if (!sc_pos(W, w4[0], &pn)) return;
-    if (!sc_pos(W, w4[1], &pp) || !sc_pos(W, w4[2], &pby)) { atomicAdd(res + 1, 1u); return; }
-    atomicAdd(res + 2, 1u);
-    Fr pw; for (int j = 0; j < 8; j++) pw.l[j] = pow256[(size_t)w4[3] * 8 + j];
-    const Fr next = sc_load(W, pn), prev = sc_load(W, pp), by = sc_load(W, pby);
-    if (!fr_eq(next, fr_add(prev, fr_mul(by, pw)))) atomicMin(res, w4[0]);
+    uint32_t w = 0;
+    const uint32_t r = sc_rel_mr(W, mw + 4 * (size_t)t, pow256, &w);
+    if (r == SC_SKIP) atomicAdd(res + 1, 1u);
+    else if (r != SC_NONE) { atomicAdd(res + 2, 1u); if (r == SC_BAD) atomicMin(res, w); }
 }
 __global__ void k_xor_word(uint64_t* p, uint64_t mask) { *p ^= mask; }
 __global__ void k_xor_u32(uint32_t* p, uint32_t mask) { *p ^= mask; }
@@ -362,7 +324,16 @@ struct pob_ctx {
         // not kept left out (counted in sc_red_host_skipped); built per map
         std::vector<std::array<uint32_t, 3>> sc_ms; std::vector<std::array<uint32_t, 2>> sc_cs;
         const int32_t* sc_alias = nullptr; uint64_t sc_alias_n = 0, sc_red_map = 0, sc_red_host_skipped = 0; uint32_t sc_red_nz = 0, sc_red_nm = 0;
-        uint32_t *d_sc_zr = nullptr, *d_sc_mr = nullptr;
+        uint32_t *d_sc_zr = nullptr, *d_sc_mr = nullptr; std::vector<uint32_t> sc_zr_host, sc_mr_host; bool sc_red_have = false;      // (host copies: pob_debug_selfcheck_sites kinds 3 / 4)
+        // group self-check (pob_emit_group_selfcheck), a switch of its own over the same site tables.  gsc_*: the O0 tables without the sites that have a wire inside a Keccak
+        // run (gsc_in_runs of them, none expected: the runs' whole blocks never reach the group's scratch); d_gsc_res: 64 verdict words + {skipped, evaluated};
+        // gsc_have: a checked group emission has run to its end (the caller has seen n_wires = 0; cleared when the next checked one begins) -- its mask, form and the sites launched
+        bool gsc_on = false, gsc_built = false, gsc_have = false, gsc_red = false;
+        std::vector<uint32_t> gsc_z, gsc_m_next, gsc_c_hi; uint32_t *d_gsc_z = nullptr, *d_gsc_m = nullptr, *d_gsc_c = nullptr, *d_gsc_res = nullptr;
+        uint64_t gsc_in_runs = 0, gsc_launched = 0, gsc_lanes = 0;
+        // pob_debug_group_emit_xor: armed for the next group emission (xor_armed), in effect during the current one (xor_now)
+        struct GXor { uint32_t lane, wire, byte; uint8_t mask; };
+        std::vector<GXor> xor_armed, xor_now;
         bool red = false; uint64_t map_id = 0, total = 0; std::vector<uint32_t> keep; unsigned long long* d_rbits = nullptr; uint32_t* d_rpre = nullptr;
         // packed windows (pob_emit_begin_packed, k_pack.hip): part of the payload KIND, like the map.  The pack pass turns the canonical window of a slot into d_pk[slot]; the header,
         // tag planes and chunk index (a length the host knows) are copied with the window, the value sections when the caller takes the window and the header's counts are in
@@ -375,7 +346,7 @@ struct pob_ctx {
         // ever touched); d_pk[2]: the 64 packed windows (stride pk_stride) of the window being expanded and of the one being copied; h_pin[3]: the selected witnesses' complete
         // packed windows, back to back, sized from the fixed parts plus the counts of the headers (h_hdr: those headers, which cross first); the third one is with the caller
         struct Group {
-            bool on = false; uint32_t group = 0, nsel = 0; uint64_t lanes = 0, alloc_wires = 0, plane = 0, pk_stride = 0, next_bulk = 0;
+            bool on = false, checked = false; uint32_t group = 0, nsel = 0; uint64_t lanes = 0, alloc_wires = 0, plane = 0, pk_stride = 0, next_bulk = 0;
             uint8_t *d_win = nullptr, *d_pk[2] = {nullptr, nullptr}, *d_hdr[2] = {nullptr, nullptr}, *h_hdr[2] = {nullptr, nullptr}, *h_pin[3] = {nullptr, nullptr, nullptr};
             uint64_t pin_cap[3] = {0, 0, 0}, off[3][64], len[3][64];
             uint32_t *d_blk = nullptr, *d_tot = nullptr;
@@ -891,7 +862,7 @@ void pob_close(pob_handle h) {
     if (!h) return;
     hipSetDevice(h->device);
     void* ptrs[] = {h->d_bits, h->d_sm, h->d_fr, h->d_units, h->d_order, h->d_L, h->d_sponges, h->d_perm_sponge, h->d_perm_block, h->d_pos,
-                    h->d_inv, h->d_pow256, h->d_ktab, h->d_emit_ctr, h->d_in_fr[0], h->d_in_fr[1], h->d_in_sm[0], h->d_in_sm[1], h->d_in_sm8[0], h->d_in_sm8[1], h->d_in_exc[0], h->d_in_exc[1], h->d_status_raw, h->d_status, h->d_chk, h->d_bad, h->d_outputs, h->d_records, h->em.d_win[0], h->em.d_win[1], h->em.d_win[2], h->em.d_order, h->em.d_probe, h->em.d_rbits, h->em.d_rpre, h->em.d_sc_z, h->em.d_sc_m, h->em.d_sc_c, h->em.d_sc_res, h->em.d_sc_zr, h->em.d_sc_mr, h->em.d_pk[0], h->em.d_pk[1], h->em.d_pk[2], h->em.d_pk_blk, h->em.d_pk_tot};
+                    h->d_inv, h->d_pow256, h->d_ktab, h->d_emit_ctr, h->d_in_fr[0], h->d_in_fr[1], h->d_in_sm[0], h->d_in_sm[1], h->d_in_sm8[0], h->d_in_sm8[1], h->d_in_exc[0], h->d_in_exc[1], h->d_status_raw, h->d_status, h->d_chk, h->d_bad, h->d_outputs, h->d_records, h->em.d_win[0], h->em.d_win[1], h->em.d_win[2], h->em.d_order, h->em.d_probe, h->em.d_rbits, h->em.d_rpre, h->em.d_sc_z, h->em.d_sc_m, h->em.d_sc_c, h->em.d_sc_res, h->em.d_sc_zr, h->em.d_sc_mr, h->em.d_gsc_z, h->em.d_gsc_m, h->em.d_gsc_c, h->em.d_gsc_res, h->em.d_pk[0], h->em.d_pk[1], h->em.d_pk[2], h->em.d_pk_blk, h->em.d_pk_tot};
     for (void* p : ptrs) if (p) hipFree(p);
     {
         pob_ctx::Emit::Group& Gr = h->em.grp;
@@ -1479,6 +1450,126 @@ static int emit_streams_and_runs(pob_ctx* h) {
 // which G units write into which window: one probe pass per (window size, map), with the single-witness kernels (what a unit writes does not depend on the witness)
 static int emit_probe_pass(pob_ctx* h, uint32_t group, uint64_t window_wires, uint64_t nwin_);
 
+// the self-check's site tables (layout constants of the handle; both switches, pob_emit_selfcheck and pob_emit_group_selfcheck, use them): the recording pass is the
+// single-witness emitter's (EmitPT<false>), run for witness idx (what it records does not depend on the witness)
+static int sc_record_sites(pob_ctx* h, uint32_t idx) {
+    pob_ctx::Emit& E = h->em;
+    for (uint32_t** q : {&E.d_sc_c, &E.d_sc_z, &E.d_sc_m, &E.d_sc_res}) { if (*q) (void)hipFree(*q); *q = nullptr; }      // (what an earlier attempt that failed half-way left behind: sc_built is still false)
+    // site-recording pass: every emitting unit once with EmitP::sites set (nothing is written); the sites are layout constants of the handle
+    const uint32_t cap = std::max(h->plan.total.q, 1u);
+    uint32_t* d_rec = nullptr;
+    const size_t words = 4 + (size_t)cap + 3 * (size_t)cap + 2 * (size_t)cap;
+    HIPC(hipMalloc(&d_rec, words * 4));
+    HIPC(hipMemsetAsync(d_rec, 0, 16, own_stream(h)));
+    GArgs A = gargs(h);
+    A.emit_sel = idx % 64; A.emit_group = idx / 64; A.emit_w0 = 0; A.emit_wn = (uint32_t)E.total; A.emit_out = nullptr; A.emit_sites = d_rec; A.emit_sites_cap = cap;
+    for (const pob_ctx::Seg& sg : h->emit_segs) { A.first = sg.first; launch_g_emit(A, sg.lds, sg.count, own_stream(h)); }
+    HIPC(hipGetLastError());
+    std::vector<uint32_t> rec(words);
+    HIPC(hipMemcpyAsync(rec.data(), d_rec, words * 4, hipMemcpyDeviceToHost, own_stream(h)));
+    HIPC(hipStreamSynchronize(own_stream(h)));
+    HIPC(hipFree(d_rec));
+    if (rec[0] > cap || rec[1] > cap || rec[2] > cap) { h->err = "internal: more self-check sites than derived wires"; return POB_E_STATE; }
+    E.sc_z.assign(rec.begin() + 4, rec.begin() + 4 + rec[0]);
+    std::sort(E.sc_z.begin(), E.sc_z.end(), [](uint32_t a, uint32_t b) { return (a & 0x7FFFFFFFu) < (b & 0x7FFFFFFFu); });
+    std::vector<std::array<uint32_t, 3>> ms(rec[1]);
+    for (uint32_t i = 0; i < rec[1]; i++) for (int j = 0; j < 3; j++) ms[i][j] = rec[4 + (size_t)cap + 3 * (size_t)i + j];
+    std::sort(ms.begin(), ms.end());
+    E.sc_ms = ms;
+    E.sc_m_next.resize(ms.size());
+    for (size_t i = 0; i < ms.size(); i++) E.sc_m_next[i] = ms[i][0];
+    std::vector<std::array<uint32_t, 2>> cs(rec[2]);
+    for (uint32_t i = 0; i < rec[2]; i++) for (int j = 0; j < 2; j++) cs[i][j] = rec[4 + 4 * (size_t)cap + 2 * (size_t)i + j];
+    std::sort(cs.begin(), cs.end());
+    E.sc_cs = cs;
+    E.sc_c_hi.resize(cs.size());
+    for (size_t i = 0; i < cs.size(); i++) E.sc_c_hi[i] = cs[i][0];
+    HIPC(hipMalloc(&E.d_sc_c, std::max<size_t>(cs.size(), 1) * 8));
+    if (!cs.empty()) HIPC(hipMemcpy(E.d_sc_c, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
+    HIPC(hipMalloc(&E.d_sc_z, std::max<size_t>(E.sc_z.size(), 1) * 4)); HIPC(hipMalloc(&E.d_sc_m, std::max<size_t>(ms.size(), 1) * 12)); HIPC(hipMalloc(&E.d_sc_res, 16));
+    if (!E.sc_z.empty()) HIPC(hipMemcpy(E.d_sc_z, E.sc_z.data(), E.sc_z.size() * 4, hipMemcpyHostToDevice));
+    if (!ms.empty()) HIPC(hipMemcpy(E.d_sc_m, ms.data(), ms.size() * 12, hipMemcpyHostToDevice));
+    E.sc_built = true;
+    return POB_OK;
+}
+// ... and the reduced form's lists for the current map (E.map_id) and alias (pob_emit_selfcheck_alias)
+static int sc_reduced_lists(pob_ctx* h) {
+    pob_ctx::Emit& E = h->em;
+    // the sites of this map: every wire through its class representative (pob_emit_selfcheck_alias; without one a wire stands for itself), a site with a wire
+    // that is pinned to a constant or not kept is left out and counted; a copy site is a tautology between class members: counted as skipped
+    const bool have_alias = E.sc_alias && E.sc_alias_n == h->plan.total.w;
+    auto rep = [&](uint32_t w, uint32_t* out, bool may_be_const = true) -> bool {
+        int64_t r = w;
+        if (have_alias) {
+            r = E.sc_alias[w];
+            if (r < 0) {                                 // pinned to a constant: -1 - c for c < 2^30, INT32_MIN for a constant that does not fit
+                if (!may_be_const || r == INT32_MIN) return false;
+                *out = 0x80000000u | (uint32_t)(-1 - r); return true;
+            }
+        }
+        if (!std::binary_search(E.keep.begin(), E.keep.end(), (uint32_t)r)) return false;
+        *out = (uint32_t)r; return true;
+    };
+    std::vector<uint32_t> zr, mr; uint64_t left_out = E.sc_cs.size();
+    for (uint32_t s0 : E.sc_z) {
+        const uint32_t w = s0 & 0x7FFFFFFFu; uint32_t q[6] = {0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        bool ok = rep(w, &q[0], false) && rep(w + 1, &q[1]) && rep(w + 2, &q[2]);
+        if (ok && (s0 >> 31)) ok = rep(w - 3, &q[3]) && rep(w - 2, &q[4]) && rep(w - 1, &q[5]);
+        if (!ok) { left_out++; continue; }
+        zr.insert(zr.end(), q, q + 6);
+    }
+    for (const std::array<uint32_t, 3>& m3 : E.sc_ms) {
+        uint32_t q[4] = {0, 0, 0, m3[2]};
+        if (!(rep(m3[0], &q[0], false) && rep(m3[0] - 1, &q[1], false) && rep(m3[1], &q[2], false))) { left_out++; continue; }
+        mr.insert(mr.end(), q, q + 4);
+    }
+    if (E.d_sc_zr) { HIPC(hipFree(E.d_sc_zr)); E.d_sc_zr = nullptr; }
+    if (E.d_sc_mr) { HIPC(hipFree(E.d_sc_mr)); E.d_sc_mr = nullptr; }
+    HIPC(hipMalloc(&E.d_sc_zr, std::max<size_t>(zr.size(), 1) * 4)); HIPC(hipMalloc(&E.d_sc_mr, std::max<size_t>(mr.size(), 1) * 4));
+    if (!zr.empty()) HIPC(hipMemcpy(E.d_sc_zr, zr.data(), zr.size() * 4, hipMemcpyHostToDevice));
+    if (!mr.empty()) HIPC(hipMemcpy(E.d_sc_mr, mr.data(), mr.size() * 4, hipMemcpyHostToDevice));
+    E.sc_red_nz = (uint32_t)(zr.size() / 6); E.sc_red_nm = (uint32_t)(mr.size() / 4); E.sc_red_host_skipped = left_out; E.sc_red_map = E.map_id;
+    E.sc_zr_host.swap(zr); E.sc_mr_host.swap(mr); E.sc_red_have = true;
+    return POB_OK;
+}
+// ... and the O0 tables of the GROUP check.  In the O0 form the Keccak runs' whole 64-wire blocks go straight into the tag planes: the group's scratch is never filled there
+// and holds stale bytes.  Every site wire is a G unit's and E.runs are the Keccak kernels' wires, so no site should have a wire in a run; one that has is left out here
+// (it counts as skipped) -- the kernels never read a position that the window's fill did not cover.  (E.runs: emit_streams_and_runs.)
+static int gsc_build_tables(pob_ctx* h) {
+    pob_ctx::Emit& E = h->em;
+    auto in_run = [&](uint32_t w) {
+        auto it = std::upper_bound(E.runs.begin(), E.runs.end(), w, [](uint32_t v, const pob_ctx::Emit::Run& r) { return v < r.w; });
+        return it != E.runs.begin() && w - (it - 1)->w < (it - 1)->n;
+    };
+    std::vector<std::array<uint32_t, 3>> ms; std::vector<std::array<uint32_t, 2>> cs;
+    E.gsc_z.clear(); E.gsc_in_runs = 0;
+    for (uint32_t s0 : E.sc_z) {
+        const uint32_t w = s0 & 0x7FFFFFFFu;
+        bool hit = in_run(w) || in_run(w + 1) || in_run(w + 2);
+        if (s0 >> 31) hit = hit || in_run(w - 3) || in_run(w - 2) || in_run(w - 1);
+        if (hit) E.gsc_in_runs++; else E.gsc_z.push_back(s0);
+    }
+    for (const std::array<uint32_t, 3>& m3 : E.sc_ms) { if (in_run(m3[0]) || in_run(m3[0] - 1) || in_run(m3[1])) E.gsc_in_runs++; else ms.push_back(m3); }
+    for (const std::array<uint32_t, 2>& c2 : E.sc_cs) { if (in_run(c2[0]) || in_run(c2[1])) E.gsc_in_runs++; else cs.push_back(c2); }
+    E.gsc_m_next.resize(ms.size()); E.gsc_c_hi.resize(cs.size());
+    for (size_t i = 0; i < ms.size(); i++) E.gsc_m_next[i] = ms[i][0];
+    for (size_t i = 0; i < cs.size(); i++) E.gsc_c_hi[i] = cs[i][0];
+    // (all or nothing: a failure frees what was allocated, so that the next checked begin starts over without a leak)
+    bool ok = hipMalloc(&E.d_gsc_z, std::max<size_t>(E.gsc_z.size(), 1) * 4) == hipSuccess && hipMalloc(&E.d_gsc_m, std::max<size_t>(ms.size(), 1) * 12) == hipSuccess &&
+              hipMalloc(&E.d_gsc_c, std::max<size_t>(cs.size(), 1) * 8) == hipSuccess && hipMalloc(&E.d_gsc_res, 66 * 4) == hipSuccess;
+    if (ok && !E.gsc_z.empty()) ok = hipMemcpy(E.d_gsc_z, E.gsc_z.data(), E.gsc_z.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !ms.empty()) ok = hipMemcpy(E.d_gsc_m, ms.data(), ms.size() * 12, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && !cs.empty()) ok = hipMemcpy(E.d_gsc_c, cs.data(), cs.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (uint32_t** q : {&E.d_gsc_z, &E.d_gsc_m, &E.d_gsc_c, &E.d_gsc_res}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+        h->err = "group self-check: out of device memory for the site tables";
+        return POB_E_NOMEM;
+    }
+    E.gsc_built = true;
+    return POB_OK;
+}
+
 // common part of pob_emit_begin / pob_emit_begin_reduced: E.red / E.map_id / E.total are set
 static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
     pob_ctx::Emit& E = h->em;
@@ -1526,85 +1617,14 @@ static int emit_start(pob_ctx* h, uint32_t idx, uint64_t window_wires) {
         E.pk_alloc_wires = E.alloc_wires;
     }
     { int rc = emit_probe_pass(h, idx / 64, window_wires, nwin_); if (rc) return rc; }
-    if (E.sc_on && !E.sc_built) {
-        // site-recording pass: every emitting unit once with EmitP::sites set (nothing is written); the sites are layout constants of the handle
-        const uint32_t cap = std::max(h->plan.total.q, 1u);
-        uint32_t* d_rec = nullptr;
-        const size_t words = 4 + (size_t)cap + 3 * (size_t)cap + 2 * (size_t)cap;
-        HIPC(hipMalloc(&d_rec, words * 4));
-        HIPC(hipMemsetAsync(d_rec, 0, 16, own_stream(h)));
-        GArgs A = gargs(h);
-        A.emit_sel = idx % 64; A.emit_group = idx / 64; A.emit_w0 = 0; A.emit_wn = (uint32_t)E.total; A.emit_out = nullptr; A.emit_sites = d_rec; A.emit_sites_cap = cap;
-        for (const pob_ctx::Seg& sg : h->emit_segs) { A.first = sg.first; launch_g_emit(A, sg.lds, sg.count, own_stream(h)); }
-        HIPC(hipGetLastError());
-        std::vector<uint32_t> rec(words);
-        HIPC(hipMemcpyAsync(rec.data(), d_rec, words * 4, hipMemcpyDeviceToHost, own_stream(h)));
-        HIPC(hipStreamSynchronize(own_stream(h)));
-        HIPC(hipFree(d_rec));
-        if (rec[0] > cap || rec[1] > cap || rec[2] > cap) { h->err = "internal: more self-check sites than derived wires"; return POB_E_STATE; }
-        E.sc_z.assign(rec.begin() + 4, rec.begin() + 4 + rec[0]);
-        std::sort(E.sc_z.begin(), E.sc_z.end(), [](uint32_t a, uint32_t b) { return (a & 0x7FFFFFFFu) < (b & 0x7FFFFFFFu); });
-        std::vector<std::array<uint32_t, 3>> ms(rec[1]);
-        for (uint32_t i = 0; i < rec[1]; i++) for (int j = 0; j < 3; j++) ms[i][j] = rec[4 + (size_t)cap + 3 * (size_t)i + j];
-        std::sort(ms.begin(), ms.end());
-        E.sc_ms = ms;
-        E.sc_m_next.resize(ms.size());
-        for (size_t i = 0; i < ms.size(); i++) E.sc_m_next[i] = ms[i][0];
-        std::vector<std::array<uint32_t, 2>> cs(rec[2]);
-        for (uint32_t i = 0; i < rec[2]; i++) for (int j = 0; j < 2; j++) cs[i][j] = rec[4 + 4 * (size_t)cap + 2 * (size_t)i + j];
-        std::sort(cs.begin(), cs.end());
-        E.sc_cs = cs;
-        E.sc_c_hi.resize(cs.size());
-        for (size_t i = 0; i < cs.size(); i++) E.sc_c_hi[i] = cs[i][0];
-        HIPC(hipMalloc(&E.d_sc_c, std::max<size_t>(cs.size(), 1) * 8));
-        if (!cs.empty()) HIPC(hipMemcpy(E.d_sc_c, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
-        HIPC(hipMalloc(&E.d_sc_z, std::max<size_t>(E.sc_z.size(), 1) * 4)); HIPC(hipMalloc(&E.d_sc_m, std::max<size_t>(ms.size(), 1) * 12)); HIPC(hipMalloc(&E.d_sc_res, 16));
-        if (!E.sc_z.empty()) HIPC(hipMemcpy(E.d_sc_z, E.sc_z.data(), E.sc_z.size() * 4, hipMemcpyHostToDevice));
-        if (!ms.empty()) HIPC(hipMemcpy(E.d_sc_m, ms.data(), ms.size() * 12, hipMemcpyHostToDevice));
-        E.sc_built = true;
-    }
+    if (E.sc_on && !E.sc_built) { int rc = sc_record_sites(h, idx); if (rc) return rc; }
     if (E.sc_on) {
         const uint32_t init[3] = {0xFFFFFFFFu, 0, 0};
         HIPC(hipMemcpyAsync(E.d_sc_res, init, 12, hipMemcpyHostToDevice, own_stream(h)));
         HIPC(hipStreamSynchronize(own_stream(h)));
         E.sc_checked = 0; E.sc_skipped = 0;
     }
-    if (E.sc_on && E.red && E.sc_red_map != E.map_id) {
-        // the sites of this map: every wire through its class representative (pob_emit_selfcheck_alias; without one a wire stands for itself), a site with a wire
-        // that is pinned to a constant or not kept is left out and counted; a copy site is a tautology between class members: counted as skipped
-        const bool have_alias = E.sc_alias && E.sc_alias_n == h->plan.total.w;
-        auto rep = [&](uint32_t w, uint32_t* out, bool may_be_const = true) -> bool {
-            int64_t r = w;
-            if (have_alias) {
-                r = E.sc_alias[w];
-                if (r < 0) {                                 // pinned to a constant: -1 - c for c < 2^30, INT32_MIN for a constant that does not fit
-                    if (!may_be_const || r == INT32_MIN) return false;
-                    *out = 0x80000000u | (uint32_t)(-1 - r); return true;
-                }
-            }
-            if (!std::binary_search(E.keep.begin(), E.keep.end(), (uint32_t)r)) return false;
-            *out = (uint32_t)r; return true;
-        };
-        std::vector<uint32_t> zr, mr; uint64_t left_out = E.sc_cs.size();
-        for (uint32_t s0 : E.sc_z) {
-            const uint32_t w = s0 & 0x7FFFFFFFu; uint32_t q[6] = {0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            bool ok = rep(w, &q[0], false) && rep(w + 1, &q[1]) && rep(w + 2, &q[2]);
-            if (ok && (s0 >> 31)) ok = rep(w - 3, &q[3]) && rep(w - 2, &q[4]) && rep(w - 1, &q[5]);
-            if (!ok) { left_out++; continue; }
-            zr.insert(zr.end(), q, q + 6);
-        }
-        for (const std::array<uint32_t, 3>& m3 : E.sc_ms) {
-            uint32_t q[4] = {0, 0, 0, m3[2]};
-            if (!(rep(m3[0], &q[0], false) && rep(m3[0] - 1, &q[1], false) && rep(m3[1], &q[2], false))) { left_out++; continue; }
-            mr.insert(mr.end(), q, q + 4);
-        }
-        if (E.d_sc_zr) { HIPC(hipFree(E.d_sc_zr)); E.d_sc_zr = nullptr; }
-        if (E.d_sc_mr) { HIPC(hipFree(E.d_sc_mr)); E.d_sc_mr = nullptr; }
-        HIPC(hipMalloc(&E.d_sc_zr, std::max<size_t>(zr.size(), 1) * 4)); HIPC(hipMalloc(&E.d_sc_mr, std::max<size_t>(mr.size(), 1) * 4));
-        if (!zr.empty()) HIPC(hipMemcpy(E.d_sc_zr, zr.data(), zr.size() * 4, hipMemcpyHostToDevice));
-        if (!mr.empty()) HIPC(hipMemcpy(E.d_sc_mr, mr.data(), mr.size() * 4, hipMemcpyHostToDevice));
-        E.sc_red_nz = (uint32_t)(zr.size() / 6); E.sc_red_nm = (uint32_t)(mr.size() / 4); E.sc_red_host_skipped = left_out; E.sc_red_map = E.map_id;
-    }
+    if (E.sc_on && E.red && E.sc_red_map != E.map_id) { int rc = sc_reduced_lists(h); if (rc) return rc; }
     for (int k = 0; k < NS; k++) HIPC(hipEventRecord(E.ev_free[k], E.s_copy));
     E.win_wires = window_wires; E.nwin = nwin_; E.idx = idx; E.next_make = 0; E.next_take = 0; E.first_slot = 0; E.active = true;
     for (; E.next_make < std::min<uint64_t>(1, E.nwin); E.next_make++) { int rc = emit_make_window(h, idx, E.next_make, (int)((E.first_slot + E.next_make) % NS)); if (rc) return rc; }
@@ -1812,6 +1832,29 @@ static int group_make_window(pob_ctx* h, uint64_t k) {
         const pob_ctx::Emit::Run& r = *c.r;
         launch_k_emit_group_canon(Gp, GW, (uint32_t)c.lo, AbsorbRef{r.b, r.prev, r.src}, (r.absorb ? r.o : r.b) + (uint32_t)(c.lo - r.w), (uint32_t)(c.hi - c.lo), r.absorb ? h->d_ktab : nullptr, st);
     }
+    for (const pob_ctx::Emit::GXor& x : E.xor_now) {                        // test hook (pob_debug_group_emit_xor): behind the expansion, in front of the check
+        if (!((Gr.lanes >> x.lane) & 1)) continue;
+        uint64_t pos = x.wire;
+        if (E.red) { const auto it = std::lower_bound(E.keep.begin(), E.keep.end(), x.wire); if (it == E.keep.end() || *it != x.wire) continue; pos = (uint64_t)(it - E.keep.begin()); }
+        if (pos < w0 || pos >= w0 + wn) continue;
+        launch_group_xor_byte(Gr.d_win + (uint64_t)x.lane * Gr.plane + (pos - w0) * 32 + x.byte, x.mask, st);
+    }
+    if (Gr.checked) {         // the derived wires' relations on the values just written into every selected witness' window: behind the scratch's last writer, in front of the pack pass
+        const ScGroup SG{Gr.d_win, Gr.plane, Gr.lanes, (uint32_t)w0, (uint32_t)wn, E.red ? E.d_rbits : nullptr, E.red ? E.d_rpre : nullptr, E.d_gsc_res, E.d_gsc_res + 64};
+        if (E.red) {          // every site whose wires are all kept (through their class representatives), at their ranks: the kernels find the window's own (lists: sc_reduced_lists)
+            launch_selfcheck_group_zr(SG, E.d_sc_zr, E.sc_red_nz, st);
+            launch_selfcheck_group_mr(SG, E.d_sc_mr, E.sc_red_nm, h->d_pow256, st);
+        } else {              // sites by the wire range of the window, as emit_make_window selects them; the kernels skip (and count) a site one of whose wires is outside the window
+            const auto za = std::lower_bound(E.gsc_z.begin(), E.gsc_z.end(), (uint32_t)wire_lo, [](uint32_t s, uint32_t v) { return (s & 0x7FFFFFFFu) < v; });
+            const auto zb = std::lower_bound(za, E.gsc_z.end(), (uint32_t)wire_hi, [](uint32_t s, uint32_t v) { return (s & 0x7FFFFFFFu) < v; });
+            launch_selfcheck_group_z(SG, E.d_gsc_z + (za - E.gsc_z.begin()), (uint32_t)(zb - za), st);
+            const auto ma = std::lower_bound(E.gsc_m_next.begin(), E.gsc_m_next.end(), (uint32_t)wire_lo), mb = std::lower_bound(ma, E.gsc_m_next.end(), (uint32_t)wire_hi);
+            launch_selfcheck_group_m(SG, E.d_gsc_m + 3 * (ma - E.gsc_m_next.begin()), (uint32_t)(mb - ma), h->d_pow256, st);
+            const auto ca = std::lower_bound(E.gsc_c_hi.begin(), E.gsc_c_hi.end(), (uint32_t)wire_lo), cb = std::lower_bound(ca, E.gsc_c_hi.end(), (uint32_t)wire_hi);
+            launch_selfcheck_group_c(SG, E.d_gsc_c + 2 * (ca - E.gsc_c_hi.begin()), (uint32_t)(cb - ca), st);
+            E.gsc_launched += (uint64_t)(zb - za) + (uint64_t)(mb - ma) + (uint64_t)(cb - ca);
+        }
+    }
     launch_pack_group(PG, w0, (uint32_t)wn, ranges, st);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(Gr.ev_made[ps], st));
@@ -1858,7 +1901,7 @@ int pob_emit_begin_group_packed(pob_handle h, uint32_t group, uint64_t lanes, co
     if (!h || !lanes_out || (!keep && n_keep) || (keep && !n_keep)) return POB_E_ARG;
     pob_ctx::Emit& E = h->em; pob_ctx::Emit::Group& Gr = E.grp;
     if (!h->generated || (uint64_t)group * 64 >= h->n) { h->err = "nothing generated / group out of range"; return POB_E_STATE; }
-    if (E.sc_on) { h->err = "group emissions are not self-checked: switch pob_emit_selfcheck off"; return POB_E_STATE; }
+    if (E.sc_on) { h->err = "pob_emit_selfcheck does not cover group emissions: switch it off and use pob_emit_group_selfcheck"; return POB_E_STATE; }
     for (const pob_ctx::Seg& sg : h->emit_segs) if (sg.lds == 5) { h->err = "group emission is for the circuits' mains, not for gadget-level mains"; return POB_E_STATE; }
     HIPC(hipSetDevice(h->device));
     HIPC(hipEventSynchronize(h->ev_gen_done));
@@ -1901,6 +1944,19 @@ int pob_emit_begin_group_packed(pob_handle h, uint32_t group, uint64_t lanes, co
         Gr.alloc_wires = window_wires;
     }
     if (lanes) { int rc = emit_probe_pass(h, group, window_wires, nwin_); if (rc) return rc; }
+    if (E.gsc_on) {           // the group check: the handle's site tables (built by whichever switch needs them first), this map's lists, 64 verdict words and the two counters
+        if (lanes) {
+            if (!E.sc_built) { int rc = sc_record_sites(h, group * 64 + (uint32_t)__builtin_ctzll(lanes)); if (rc) return rc; }
+            if (!E.gsc_built) { int rc = gsc_build_tables(h); if (rc) return rc; }
+            if (E.red && E.sc_red_map != E.map_id) { int rc = sc_reduced_lists(h); if (rc) return rc; }
+            uint32_t init[66]; for (int l = 0; l < 64; l++) init[l] = 0xFFFFFFFFu; init[64] = init[65] = 0;
+            HIPC(hipMemcpyAsync(E.d_gsc_res, init, sizeof init, hipMemcpyHostToDevice, own_stream(h)));
+            HIPC(hipStreamSynchronize(own_stream(h)));
+        }
+        E.gsc_have = false; E.gsc_lanes = lanes; E.gsc_red = E.red; E.gsc_launched = 0;
+    }
+    Gr.checked = E.gsc_on;
+    E.xor_now.swap(E.xor_armed); E.xor_armed.clear();                       // (pob_debug_group_emit_xor: this emission only)
     Gr.on = true; Gr.group = group; Gr.lanes = lanes; Gr.nsel = (uint32_t)__builtin_popcountll(lanes); Gr.next_bulk = 0;
     *lanes_out = lanes;
     E.win_wires = window_wires; E.nwin = lanes ? nwin_ : 0; E.idx = group * 64; E.next_make = 0; E.next_take = 0; E.first_slot = 0; E.active = true;
@@ -1915,7 +1971,7 @@ int pob_emit_next_group_packed(pob_handle h, const uint8_t* data[64], uint64_t b
     if (!E.active) { h->err = "pob_emit_next_group_packed without pob_emit_begin_group_packed"; return POB_E_STATE; }
     if (!Gr.on) { h->err = "pob_emit_next_group_packed: the emission was not begun with pob_emit_begin_group_packed"; return POB_E_STATE; }
     for (int l = 0; l < 64; l++) { data[l] = nullptr; bytes[l] = 0; }
-    if (E.next_take == E.nwin) { E.active = false; *first_wire = E.nwin ? E.total : 0; *n_wires = 0; return POB_OK; }
+    if (E.next_take == E.nwin) { E.active = false; if (Gr.checked) E.gsc_have = true; *first_wire = E.nwin ? E.total : 0; *n_wires = 0; return POB_OK; }
     HIPC(hipSetDevice(h->device));
     const uint64_t k = E.next_take;
     // the window handed out by the previous call is released now.  Window k + 1's headers have crossed (or are about to): its copies are queued behind window k's, and with
@@ -1960,6 +2016,66 @@ int pob_emit_selfcheck_result(pob_handle h, uint64_t* checked, uint64_t* skipped
     if (checked) *checked = done;
     if (skipped) *skipped = all - done;
     if (first_bad_wire) *first_bad_wire = res[0];
+    return POB_OK;
+}
+
+int pob_emit_group_selfcheck(pob_handle h, int enable) {
+    if (!h) return POB_E_ARG;
+    h->em.gsc_on = enable != 0;
+    return POB_OK;
+}
+
+int pob_emit_group_selfcheck_result(pob_handle h, uint64_t* lanes, uint64_t* checked, uint64_t* skipped, uint32_t first_bad_wire[64]) {
+    if (!h) return POB_E_ARG;
+    pob_ctx::Emit& E = h->em;
+    if (!E.gsc_have) { h->err = "no complete self-checked group emission (pob_emit_group_selfcheck, then a group emission read to n_wires = 0: windows are made ahead of the caller)"; return POB_E_STATE; }
+    uint32_t res[66]; for (int l = 0; l < 64; l++) res[l] = 0xFFFFFFFFu; res[64] = res[65] = 0;
+    uint64_t all = 0, done = 0;
+    if (E.gsc_lanes) {
+        HIPC(hipSetDevice(h->device));
+        HIPC(hipStreamSynchronize(own_stream(h)));
+        HIPC(hipMemcpy(res, E.d_gsc_res, sizeof res, hipMemcpyDeviceToHost));
+        all = E.sc_z.size() + E.sc_m_next.size() + E.sc_c_hi.size();
+        done = E.gsc_red ? (uint64_t)res[65] : E.gsc_launched - res[64];      // (reduced: the kernels count what they evaluate; O0: what was launched less what they skipped)
+    }
+    if (lanes) *lanes = E.gsc_lanes;
+    if (checked) *checked = done;
+    if (skipped) *skipped = all - done;
+    if (first_bad_wire) for (int l = 0; l < 64; l++) first_bad_wire[l] = ((E.gsc_lanes >> l) & 1) ? res[l] : 0xFFFFFFFFu;
+    return POB_OK;
+}
+
+int pob_debug_selfcheck_sites(pob_handle h, int kind, uint32_t* out, uint64_t cap, uint64_t* n) {
+    if (!h || !n || kind < 0 || kind > 4) return POB_E_ARG;
+    pob_ctx::Emit& E = h->em;
+    if (kind >= 3) {          // the reduced lists of the last checked reduced emission (either switch): as they are, nothing is built
+        const std::vector<uint32_t>& v = kind == 3 ? E.sc_zr_host : E.sc_mr_host;
+        if (!E.sc_red_have) { h->err = "no checked reduced emission yet"; return POB_E_STATE; }
+        *n = v.size();
+        if (out) { if (cap < v.size()) return POB_E_ARG; if (!v.empty()) memcpy(out, v.data(), v.size() * 4); }
+        return POB_OK;
+    }
+    if (!E.sc_built) {
+        if (!h->generated) { h->err = "nothing generated"; return POB_E_STATE; }
+        HIPC(hipSetDevice(h->device));
+        HIPC(hipEventSynchronize(h->ev_gen_done));
+        if (h->evaluated) HIPC(hipEventSynchronize(h->ev_check_done));
+        int rc = sc_record_sites(h, 0); if (rc) return rc;
+    }
+    const uint32_t* src = kind == 0 ? E.sc_z.data() : kind == 1 ? (const uint32_t*)E.sc_ms.data() : (const uint32_t*)E.sc_cs.data();
+    const uint64_t words = kind == 0 ? E.sc_z.size() : kind == 1 ? 3 * E.sc_ms.size() : 2 * E.sc_cs.size();
+    *n = words;
+    if (out) {
+        if (cap < words) return POB_E_ARG;
+        if (words) memcpy(out, src, words * 4);
+    }
+    return POB_OK;
+}
+
+int pob_debug_group_emit_xor(pob_handle h, uint32_t lane, uint32_t wire, uint32_t byte, uint8_t mask) {
+    if (!h || lane >= 64 || byte >= 32 || wire >= h->plan.total.w) return POB_E_ARG;
+    if (h->em.xor_armed.size() >= 16) { h->err = "pob_debug_group_emit_xor: at most 16 entries per emission"; return POB_E_ARG; }
+    h->em.xor_armed.push_back({lane, wire, byte, mask});
     return POB_OK;
 }
 

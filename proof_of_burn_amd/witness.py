@@ -194,6 +194,11 @@ def load_library() -> ctypes.CDLL:
         lib.pob_write_wtns_group.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p)]
         lib.pob_emit_measure_group.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(lib, "pob_emit_group_selfcheck"):         # (absent in an older build named by POB_LIB_PATH: tools/emit_rate.py --parent)
+        lib.pob_emit_group_selfcheck.argtypes = [vp, ctypes.c_int]
+        lib.pob_emit_group_selfcheck_result.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+        lib.pob_debug_selfcheck_sites.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        lib.pob_debug_group_emit_xor.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8]
     lib.pob_time_kernel.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
     lib.pob_probe_check_kernel.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     lib.pob_debug_xor_bits.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
@@ -221,7 +226,7 @@ EXPORTED_SYMBOLS = ["pob_plan_info", "pob_gadget_template", "pob_open", "pob_clo
                     "pob_upload_inputs8", "pob_upload_inputs8_async", "pob_narrow_inputs", "pob_pack_json_batch8",
                     "pob_results_fetch", "pob_results_wait", "pob_emit_begin_reduced", "pob_reduced_map_pin", "pob_write_wtns_reduced", "pob_emit_measure_ex", "pob_generate",
                     "pob_constraint_check", "pob_sync", "pob_set_partner", "pob_results", "pob_results_device", "pob_results_records_device", "pob_gather_records", "pob_emit_witness",
-                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
+                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_emit_group_selfcheck", "pob_emit_group_selfcheck_result", "pob_debug_selfcheck_sites", "pob_debug_group_emit_xor", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
 
 
 def plan_info(main: str) -> PobInfo:
@@ -927,6 +932,48 @@ class WitnessCalculator:
                                                  out.ctypes.data if out is not None else None, out.nbytes if out is not None else 0, threads,
                                                  ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(nb)))
         return s0.value, (s1.value if out is not None else None), nb.value
+
+    def emit_group_selfcheck(self, enable: bool = True):
+        """every following group emission evaluates the derived wires' relations on the values written for every selected witness (pob_emit_group_selfcheck); the
+        single-witness switch, emit_selfcheck, does not cover group emissions"""
+        self._ck(self.lib.pob_emit_group_selfcheck(self.h, 1 if enable else 0))
+
+    def emit_group_selfcheck_result(self) -> dict:
+        """of the last complete self-checked group emission: the mask emitted, relations checked / skipped per witness, and per selected lane the lowest violated wire
+        (None = clean)"""
+        m, c, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        w = (ctypes.c_uint32 * 64)()
+        self._ck(self.lib.pob_emit_group_selfcheck_result(self.h, ctypes.byref(m), ctypes.byref(c), ctypes.byref(s), w))
+        return {"lanes": int(m.value), "checked": int(c.value), "skipped": int(s.value),
+                "first_bad_wire": {l: (None if w[l] == 0xFFFFFFFF else int(w[l])) for l in range(64) if (m.value >> l) & 1}}
+
+    def debug_selfcheck_sites(self):
+        """the recorded O0 site tables of the self-checks, sorted by wire (pob_debug_selfcheck_sites): IsZero words [n] (bit 31: child of an IsEqual), M triples [n, 3]
+        {M[k+1], mainInput[k], k}, copy pairs [n, 2] {higher wire, lower wire}; needs a generated batch"""
+        out = []
+        for kind, cols in ((0, 1), (1, 3), (2, 2)):
+            n = ctypes.c_uint64()
+            self._ck(self.lib.pob_debug_selfcheck_sites(self.h, kind, None, 0, ctypes.byref(n)))
+            a = np.zeros(max(int(n.value), 1), dtype=np.uint32)
+            self._ck(self.lib.pob_debug_selfcheck_sites(self.h, kind, a.ctypes.data, a.size, ctypes.byref(n)))
+            a = a[:int(n.value)]
+            out.append(a if cols == 1 else a.reshape(-1, cols))
+        return tuple(out)
+
+    def debug_selfcheck_reduced_lists(self):
+        """the reduced form's site lists of the last checked reduced emission (pob_debug_selfcheck_sites kinds 3 / 4): IsZero sites [n, 6], M steps [n, 4]"""
+        out = []
+        for kind, cols in ((3, 6), (4, 4)):
+            n = ctypes.c_uint64()
+            self._ck(self.lib.pob_debug_selfcheck_sites(self.h, kind, None, 0, ctypes.byref(n)))
+            a = np.zeros(max(int(n.value), 1), dtype=np.uint32)
+            self._ck(self.lib.pob_debug_selfcheck_sites(self.h, kind, a.ctypes.data, a.size, ctypes.byref(n)))
+            out.append(a[:int(n.value)].reshape(-1, cols))
+        return tuple(out)
+
+    def debug_group_emit_xor(self, lane: int, wire: int, byte: int = 0, mask: int = 1):
+        """the NEXT group emission only: one byte of lane's canonical value of `wire` is XORed with mask after the expansion and before the check (pob_debug_group_emit_xor)"""
+        self._ck(self.lib.pob_debug_group_emit_xor(self.h, lane, wire, byte, mask))
 
     def time_kernel(self, which: int, iters: int = 5, stream: int | None = None) -> float:
         ms = ctypes.c_float()

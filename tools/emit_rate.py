@@ -7,6 +7,9 @@
     python tools/emit_rate.py --group [--pairs N] [--parent LIB]
         the group emission (pob_emit_measure_group: all 64 witnesses of the group in one pass) beside the single-witness packed path -- of the parent's library with
         --parent, else of this one -- taking turns; per form: ms per witness into pinned memory, with the host expansion, and D2H bytes per witness.
+    python tools/emit_rate.py --group-selfcheck [--pairs N] --parent LIB
+        the group emission's self-check (pob_emit_group_selfcheck): the parent's group emission, this library's with the check off and on, and the parent's 64 checked
+        single-witness emissions, taking turns; medians per group, the check's cost per witness
     python tools/emit_rate.py --trace-one [--group]      ONE packed O0 production emission (--group: one group emission) and nothing else after the generation (for
                                                          rocprofv3 --kernel-trace --stats)"""
 import json
@@ -81,6 +84,31 @@ def serve():
             p1, e1, d1 = calc.emit_throughput_group(0, 1, 0, keep=keep, out=buf)
             print(json.dumps({"o0_pinned_ms": p0 / 64 * 1e3, "o0_expanded_ms": e0 / 64 * 1e3, "o0_d2h": d0 // 64,
                               "red_pinned_ms": p1 / 64 * 1e3, "red_expanded_ms": e1 / 64 * 1e3, "red_d2h": d1 // 64}), flush=True)
+        elif cmd in ("group_pinned", "group_checked"):               # one group of 64 into pinned memory, no host expansion; group_checked: with pob_emit_group_selfcheck on
+            if cmd == "group_checked":
+                calc.emit_group_selfcheck(True)
+            if cmd not in warm:
+                calc.emit_throughput_group(0, 1, 0); calc.emit_throughput_group(0, 1, 0, keep=keep); warm.add(cmd)
+            p0, _, d0 = calc.emit_throughput_group(0, 1, 0)
+            r0 = calc.emit_group_selfcheck_result() if cmd == "group_checked" else None
+            p1, _, d1 = calc.emit_throughput_group(0, 1, 0, keep=keep)
+            r1 = calc.emit_group_selfcheck_result() if cmd == "group_checked" else None
+            if cmd == "group_checked":
+                calc.emit_group_selfcheck(False)
+                assert all(w is None for r in (r0, r1) for w in r["first_bad_wire"].values()) and r0["lanes"] == r1["lanes"] == (1 << 64) - 1
+            print(json.dumps({"o0_ms": p0 * 1e3, "red_ms": p1 * 1e3, "o0_d2h": d0, "red_d2h": d1,
+                              "o0_checked": r0 and [r0["checked"], r0["skipped"]], "red_checked": r1 and [r1["checked"], r1["skipped"]]}), flush=True)
+        elif cmd == "single_checked":                                 # the only checked alternative without the group check: 64 single-witness packed emissions with pob_emit_selfcheck on
+            calc.emit_selfcheck(True)
+            if cmd not in warm:
+                calc.emit_throughput_packed(0, 1, 4 << 20); calc.emit_throughput_packed(0, 1, 4 << 20, keep=keep); warm.add(cmd)
+            p0, _, d0 = calc.emit_throughput_packed(0, 64, 4 << 20)
+            r0 = calc.emit_selfcheck_result()
+            p1, _, d1 = calc.emit_throughput_packed(0, 64, 4 << 20, keep=keep)
+            r1 = calc.emit_selfcheck_result()
+            calc.emit_selfcheck(False)
+            assert r0["first_bad_wire"] is None and r1["first_bad_wire"] is None
+            print(json.dumps({"o0_ms": p0 * 1e3, "red_ms": p1 * 1e3, "o0_d2h": d0, "red_d2h": d1, "o0_checked": [r0["checked"], r0["skipped"]], "red_checked": [r1["checked"], r1["skipped"]]}), flush=True)
         elif cmd == "unpack":
             from proof_of_burn_amd import witness as W
             if buf is None:
@@ -175,6 +203,37 @@ def group(pairs, parent):
         print(f"  witnesses per second, group / single: {a / b:.1f} x")
 
 
+def group_selfcheck(pairs, parent):
+    """four legs, one production group of 64 at the group path's default window (4 Mi wires), into pinned memory: (a) the parent's library, group emission; (b) this
+    library, pob_emit_group_selfcheck off; (c) on; (d) the parent's only checked alternative, 64 single-witness packed emissions with pob_emit_selfcheck on (at the same
+    window size, so that the same sites straddle windows)"""
+    new = Proc()
+    old = Proc(parent)
+    legs = (("a", old, "group_pinned"), ("b", new, "group_pinned"), ("c", new, "group_checked"), ("d", old, "single_checked"))
+    rows = {k: [] for k, _, _ in legs}
+    try:
+        for _, who, cmd in legs:                                      # warm-up: allocations, probe and recording passes
+            who.ask(cmd)
+        for _ in range(pairs):                                        # the four legs take turns on one GPU
+            for k, who, cmd in legs:
+                rows[k].append(who.ask(cmd))
+    finally:
+        old.close(); new.close()
+    names = {"a": "(a) parent library, group emission of 64             ", "b": "(b) this library, group emission, check off          ",
+             "c": "(c) this library, group emission, check on           ", "d": "(d) parent library, 64 single emissions, check on    "}
+    print(f"{MAIN}, one calculator, 64 witnesses resident; one group of 64 into pinned memory, window 4 Mi wires; {pairs} rounds, the four legs taking turns on one GPU; ms per GROUP")
+    for form, key in (("O0 (215 907 954 wires)", "o0"), ("reduced (21 454 032 kept wires)", "red")):
+        print(f"{form}:")
+        med = {}
+        for k in "abcd":
+            xs = [r[key + "_ms"] for r in rows[k]]
+            med[k] = statistics.median(xs)
+            chk = rows[k][0][key + "_checked"]
+            print(f"  {names[k]} {_fmt(xs)}; {rows[k][0][key + '_d2h']} B D2H" + (f"; per witness {chk[0]} relations checked, {chk[1]} skipped" if chk else ""))
+        print(f"  cost of the check (c - b): {med['c'] - med['b']:.2f} ms per group = {(med['c'] - med['b']) / 64 * 1e3:.1f} us per witness ({(med['c'] / med['b'] - 1) * 100:+.1f} %)")
+        print(f"  checked witnesses per second, (d) / (c): {med['d'] / med['c']:.1f} x")
+
+
 def trace_one():
     if "--group" in sys.argv:
         calc, _ = open_calc()
@@ -194,6 +253,8 @@ if __name__ == "__main__":
         serve()
     elif "--trace-one" in a:
         trace_one()
+    elif "--group-selfcheck" in a:
+        group_selfcheck(int(a[a.index("--pairs") + 1]) if "--pairs" in a else 7, a[a.index("--parent") + 1])
     elif "--group" in a:
         group(int(a[a.index("--pairs") + 1]) if "--pairs" in a else 7, a[a.index("--parent") + 1] if "--parent" in a else None)
     elif "--packed" in a:
