@@ -133,7 +133,8 @@ void pob_host_free(void* p);
 int pob_generate(pob_handle h, void* stream);
 /* Per-gate constraint evaluator over the resident witness vector (north star; the reference checks inline,
  * e.g. assert.circom:46,62,78, divide.circom:32): re-reads every STORED wire and checks it against its defining expression evaluated on
- * STORED operands, and every `===`; asynchronous.  Wires without storage are not read: a derived wire's (n_derived) relations hold by
+ * STORED operands, and every `===`; asynchronous.  (A calculator whose evaluation rode with its generation -- pob_set_inorder bit 2 -- skips most of these launches: what
+ * riding establishes instead, and the audit that runs them for sampled groups, are described at pob_set_inorder / pob_set_audit.)  Wires without storage are not read: a derived wire's (n_derived) relations hold by
  * construction in whatever the emitter writes for it, an alias wire's (n_alias) copy constraint holds structurally, and every non-copy
  * gate that consumes one is evaluated on the stored wire it stands for.  pob_emit_begin*'s self-check (POB_EMIT_SELFCHECK) evaluates the
  * derived / alias wires' own relations on the values as written.                                                  */
@@ -160,8 +161,30 @@ int pob_set_partner(pob_handle h, pob_handle partner);
  * pob_constraint_check's round kernel does; pob_constraint_check then skips that kernel (1.77 of the 2.27 GB it would read per 1 024 production witnesses); the input rows are compared with the
  * inputs by the launch that writes them (k_inputs MODE 2), and -- for the two main circuits -- every G unit's stores are loaded back and compared by the unit itself
  * (policy.hpp GenPT<true>, poseidon_wide.hpp PosWideT<true>; the RLP units excepted): of the evaluation pass pob_constraint_check then runs the sponge chains' kernel and the
- * RLP family's and collects the records -- unless a debug poke touched the vector in between, in which case it runs everything.  Same records, same failing sites. */
+ * RLP family's and collects the records -- unless a debug poke touched the vector in between, in which case it runs everything.  Same records, same failing sites on every
+ * input the tests know.
+ * WHAT RIDING ESTABLISHES.  For the round blocks the riding launch checks every gate on loaded values.  For the G units and the Poseidon blocks it is a STORE VERIFICATION: each
+ * stored wire is loaded back and compared with the value the generator itself just COMPUTED for it, and every `===` is evaluated on computed operands.  That shows the
+ * resident vector is what the generator meant to write; it is not an evaluation of the constraints.  Where generator and constraint take different routes (the lane-spread
+ * Poseidon blocks against the evaluator's segments, Num2BigEndianBytes, the is_gen branches of the gadgets) a generator bug or an ALU fault leaves the riding verdict
+ * clean.  The independent evaluation -- CheckP, k_rounds_check, the input check: every stored wire against its definition on STORED operands -- of a riding calculator is
+ * pob_set_audit, below, or a calculator without bit 2. */
 int pob_set_inorder(pob_handle h, int on);
+/* AUDIT MODE: the independent evaluation of sampled groups beside riding (replaces nothing in the reference, whose calculator checks inline, one witness per process, Makefile:4-5;
+ * DESIGN.md section 4.3, ADVICE.md's first item).  groups = 0: off (the default).  groups > 0: every period-th pob_constraint_check of the handle (the first one after this
+ * call included; period = 0 is POB_E_ARG) that skips launches because the generation rode (pob_set_inorder bit 2) runs them after all for a WINDOW of consecutive groups of 64
+ * witnesses: the round kernel, the input check and -- where the G units rode -- the narrow kernel and the wide families, each as one extra launch on the caller's stream ahead of
+ * the record collection; the sponge chains' kernel and the RLP family's run over all groups as before.  The records carry the lower of the riding verdict and the
+ * evaluator's.  Window: [first, first + n), n = min(groups, G - first) for a batch of G groups; `first` starts at 0, advances by n per audited batch, returns to 0 when it
+ * reaches G (or finds itself >= G in a smaller batch) and never wraps inside a batch: with groups = k any ceil(G / k) consecutive audited batches of equal size cover every
+ * group, groups >= G audits whole batches.  No randomness: a caller who wants a random phase calls pob_set_audit again, which resets the cursor, the period count and the totals.
+ * Every pob_constraint_check of the handle counts towards the period, also one that did not ride (track schedule, a debug poke since the generation) and evaluated everything
+ * anyway: such a check shifts the phase of the audited batches.  With the audit off pob_constraint_check enqueues exactly what it did before.
+ * pob_audit_last: what the handle's last pob_constraint_check evaluated independently -- n_groups = 0: nothing (audit off, an off-period batch, no check yet); (0, G): everything
+ * anyway (track schedule, in-order without bit 2, a debug poke since the generation); else the audit window -- and the audited batches / groups since pob_set_audit (window
+ * audits only).  Any pointer may be NULL. */
+int pob_set_audit(pob_handle h, uint32_t groups, uint32_t period);
+int pob_audit_last(pob_handle h, uint32_t* first_group, uint32_t* n_groups, uint64_t* audited_batches, uint64_t* audited_groups);
 
 /* Replaces "stderr non-empty => failure" + the output dump patched in by tests/test.py:36-54.
  * status[i] = 0 ok, else (template id << 12 | source line) of the first failing assert; outputs[i][32] = public
@@ -352,6 +375,15 @@ int pob_debug_xor_bits(pob_handle h, uint32_t group, uint64_t bit_index, uint64_
  * row of a ProofOfBurn main: the input's wire -- else 0xFFFFFFFF: a store of a G unit (reported at the wire itself) if a riding unit stores the word at all (the sponge chains'
  * words and the RLP units' wires are stored by launches that do not evaluate).  POB_E_ARG: no such word.  One generation, then disarmed. */
 int pob_debug_store_fault(pob_handle h, int cls, uint32_t group, uint64_t index, uint64_t mask, uint32_t* wire);
+/* Test hook for the audit (pob_set_audit; replaces nothing in the reference): a fault of the GENERATOR.  Armed like pob_debug_store_fault (riding
+ * calculators, one generation, mask = 0 disarms), but the value is wrong BEFORE the store -- bit 0 of an SM value / of the lowest limb of an FR element flipped for the witnesses of
+ * mask -- and the unit goes on with it: put / hint return the corrupted value, the load-back agrees, the riding verdict stays clean by construction.  Only an evaluation that
+ * recomputes the wire from its stored operands sees it.  Covered: SM and FR puts of the riding G units, and the elements of the lane-spread Poseidon blocks that carry the
+ * running state (Ark0.out, each full round's Ark.out and Mix.out, each partial round's MixS.out).  POB_E_ARG with "not covered" in pob_strerror: BIT words (round blocks,
+ * sponge chains, bit runs), input rows, the RLP units' wires (plain policy), the other elements of a Poseidon block; "no such word": a rank outside the class.  *wire (may be
+ * NULL): the O0 wire of a Poseidon element, else 0xFFFFFFFF -- as for pob_debug_store_fault, a rank that no riding put writes arms nothing.  mask = 0 arms nothing and disarms a pending
+ * value fault only (a pending pob_debug_store_fault stays armed): the return value then just says whether the word is covered.  Data is corrupted, never an address. */
+int pob_debug_value_fault(pob_handle h, int cls, uint32_t group, uint64_t index, uint64_t mask, uint32_t* wire);
 /* Experiment hook (profiles/round6_experiments.txt 9): a non-blocking stream of `device` restricted to the compute units of cu_mask (hipExtStreamCreateWithCUMask; words x 32 bits,
  * bit i = CU i), for callers that want to partition the device between calculators.  pob_debug_stream_destroy frees it. */
 int pob_debug_stream_create(int device, const uint32_t* cu_mask, uint32_t words, void** stream);

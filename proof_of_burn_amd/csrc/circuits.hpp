@@ -188,6 +188,20 @@ HD PosOff pos_off(int t) {
     return k;
 }
 
+// pob_debug_value_fault: the elements of a Poseidon(T - 1) block (rel = FR rank - the block's first) whose store carries the running state, so that a value fault there
+// propagates -- Ark0.out, every full round's Ark.out and Mix.out, every partial round's MixS.out (poseidon_wide.hpp posw_run assigns what st() returns at exactly these).  The Sigma
+// internals, the operand copies and the head / tail copies of the hash are stored from values the lanes already hold: not covered (the hook refuses them)
+HD bool posw_value_fault_covers(int T, uint32_t rel) {
+    const uint32_t t = (uint32_t)T, rp = (uint32_t)pos_off(T).rp, full = 8 * t, part = 4 + 2 * t;
+    if (rel < 4 * t + 1) return rel >= 2 * t + 1 && rel <= 3 * t;
+    rel -= 4 * t + 1;
+    if (rel >= 4 * full && rel < 4 * full + rp * part) { const uint32_t q = (rel - 4 * full) % part; return q >= 4 && q < 4 + t; }
+    if (rel >= 4 * full) rel -= rp * part;
+    if (rel >= 7 * full) return false;
+    const uint32_t q = rel % full;
+    return (q >= 4 * t && q < 5 * t) || (q >= 6 * t && q < 7 * t);
+}
+
 // ---------------------------------------------------------------------------- keccak.circom: Pad / KeccakBytes
 // KeccakBytes(mb) :454-489 up to Pad's loops:
 // [out[32] | in[m], inLen | padded[m], numBlocks, inBitsArray[m][8], inBits[8m], inBlocks[mb][17][64], outBits[256], outBytes[32][8]]

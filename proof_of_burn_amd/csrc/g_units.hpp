@@ -9,7 +9,7 @@ template <class P, uint32_t MASK> __device__ __forceinline__ void g_units_body(c
     // the few long BN254 chains share their SIMDs with thousands of short light / Keccak waves: let the arbiter favour them
     if constexpr ((MASK & ~FAM_LIGHT) != 0) __builtin_amdgcn_s_setprio(3);
     const uint32_t lane = threadIdx.x;
-    const uint32_t g = P::is_emit ? A.emit_group : g_in;
+    const uint32_t g = P::is_emit ? A.emit_group : P::is_check ? A.group0 + g_in : g_in;      // (evaluation: the launch covers the groups [group0, group0 + grid.x))
     P p;
     p.m.bits = A.bits + (uint64_t)g * A.bits_stride;
     p.m.sm = A.sm + (uint64_t)g * A.sm_stride;

@@ -458,7 +458,10 @@ template <int KR> __global__ void __launch_bounds__(64) k_rounds_gen(KArgs A) { 
             io.bad = 0; \
         } \
     } } while (0)
-template <bool NT, int KR, int WAVES, int DP> __global__ void __launch_bounds__(64) POB_WAVES_PER_SIMD(WAVES) k_rounds_check(KArgs A) { POB_ROUNDS_CHECK_BODY(A, blockIdx.x, blockIdx.y, NT, KR, DP); }
+template <bool NT, int KR, int WAVES, int DP> __global__ void __launch_bounds__(64) POB_WAVES_PER_SIMD(WAVES) k_rounds_check(KArgs A) {
+    const uint32_t g = A.group0 + blockIdx.y;              // the launch covers the groups [group0, group0 + grid.y)
+    POB_ROUNDS_CHECK_BODY(A, blockIdx.x, g, NT, KR, DP);
+}
 
 // Generation AND constraint evaluation of the round blocks in one launch (in-order calculators, pob_set_inorder bit 2).  The wavefront of (permutation, KR rounds, group)
 // stores each of the 76 gate-output arrays of a round and requests the SAME array back from memory right behind the store; DP gates later the loaded array is compared with

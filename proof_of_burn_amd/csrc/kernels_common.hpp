@@ -8,6 +8,7 @@
 
 typedef unsigned long long u64;
 
+#define FAULT_VALUE 0x100u      // flag in fault_cls (low byte: the storage class)
 struct GArgs {
     const UnitDesc* units; const uint32_t* order; uint32_t first;
     CircuitLayout* L;                                  // read-only on the device (only the host planner writes reference tables)
@@ -22,8 +23,9 @@ struct GArgs {
     const unsigned long long* emit_rbits; const uint32_t* emit_rpre;   // reduced witness: kept-wire bitmap + per-word rank (policy.hpp EmitP); null = O0 payload
     uint32_t* emit_sites; uint32_t emit_sites_cap;     // self-check site-recording pass (policy.hpp EmitP::sites)
     uint32_t* emit_counters;                           // which of the emitter's inverse paths ran (policy.hpp EmitP::ctr, pob_debug_emit_counters)
-    uint32_t fault_cls, fault_group, fault_idx; uint64_t fault_lanes;      // pob_debug_store_fault (tests): the riding kernels' FAULT instantiations (policy.hpp GenPT<true, true>, poseidon_wide.hpp); fault_cls 0xFFFFFFFF = none
+    uint32_t fault_cls, fault_group, fault_idx; uint64_t fault_lanes;      // pob_debug_store_fault / pob_debug_value_fault (tests): the riding kernels' FAULT instantiations (policy.hpp GenPT<true, true>, poseidon_wide.hpp); fault_cls 0xFFFFFFFF = none, | FAULT_VALUE = the unit goes on with the corrupted value
     uint64_t emit_plane, emit_lanes;                   // group emission (policy.hpp EmitPT<true>): witness l's canonical window at emit_out + l * emit_plane; bit l = witness l is emitted
+    uint32_t group0;                                   // evaluation launches (CheckP): the grid's first group -- block x works on group group0 + x (the audit window of pob_set_audit); everything else passes 0 and does not read it
 };
 struct KArgs {
     u64* bits;                 // BIT slabs, all groups
@@ -34,6 +36,7 @@ struct KArgs {
     uint32_t* bad_wire;        // per witness: lowest inconsistent wire (CheckIO)
     uint32_t first, count;
     uint32_t fault_group; uint64_t fault_word, fault_mask;   // k_rounds_gc<FAULT> (tests): the store at BIT word fault_word of group fault_group goes out XORed with fault_mask
+    uint32_t group0;           // k_rounds_check: the grid's first group (the audit window of pob_set_audit); the other kernels do not read it
 };
 
 // where an Absorb block's words live, for the emitter's alias map (keccak_kernels.hpp absorb_wire_word): BIT rank of the block's first stored word, of the previous

@@ -65,11 +65,12 @@ extern __shared__ uint32_t g_lds[];
 // back through a pointer the compiler cannot identify with the one stored through, and compared with the inputs
 #define POB_OPAQUE_PTR(p, T) ({ uint32_t zero_ = 0; POB_OPAQUE_S(zero_); (T)(p) + zero_; })
 // (fault_k / fault_g / fault_lanes, MODE 2, tests: input row fault_k of group fault_g reaches memory with bit 0 flipped for the witnesses of fault_lanes; 0xFFFFFFFF = none)
+// (group0, MODE 1: the launch checks the groups [group0, group0 + grid.y) -- the audit window of pob_set_audit; the generating modes do not read it)
 template <int MODE> __global__ void __launch_bounds__(64) k_inputs(const int32_t* in_sm, uint32_t nsm, int32_t* sm, uint64_t sm_stride, uint32_t s0, uint32_t w0, uint32_t* bad_wire,
-                                                                   uint32_t fault_k, uint32_t fault_g, uint64_t fault_lanes) {
+                                                                   uint32_t fault_k, uint32_t fault_g, uint64_t fault_lanes, uint32_t group0) {
     constexpr bool CHECK = MODE == 1;
     int32_t* t = (int32_t*)g_lds;                         // [64 witnesses][65]
-    const uint32_t lane = threadIdx.x, k0 = blockIdx.x * 64, g = blockIdx.y;
+    const uint32_t lane = threadIdx.x, k0 = blockIdx.x * 64, g = CHECK ? group0 + blockIdx.y : blockIdx.y;
     const int32_t* src = in_sm + (uint64_t)g * 64 * nsm;
     for (uint32_t w = 0; w < 64; w++) t[w * 65 + lane] = (k0 + lane < nsm) ? src[(uint64_t)w * nsm + k0 + lane] : 0;
     __syncthreads();
@@ -87,17 +88,17 @@ template <int MODE> __global__ void __launch_bounds__(64) k_inputs(const int32_t
     }
     if (MODE) { if (bad != 0xFFFFFFFFu) atomicMin(&bad_wire[g * 64 + lane], bad); }
 }
-static void launch_inputs(pob_ctx* h, int mode, uint32_t G, hipStream_t st);
+static void launch_inputs(pob_ctx* h, int mode, uint32_t G, hipStream_t st, uint32_t group0 = 0);
 // The same from the BYTE FORM of a batch (pob_upload_inputs8*: u8 rows + POB_EXC_CAP exception slots per witness), in ONE pass: a workgroup reads 64 witnesses x 128 inputs as
 // bytes (32 per thread), widens them into an LDS tile, lays the group's exception slots that fall into its 128 inputs over the tile, and writes (CHECK: compares) the 128 SM
 // rows, lane = witness.  Rounds 4-5 widened the whole batch into an int32 copy of the packed inputs first (k_widen_sm8 + k_apply_exc on the upload stream: 11 MB read, 45 MB
 // written) and transposed that copy (45 MB read, 45 MB written): per batch two launches and 90 MB of traffic that this pass does not have.  grid = (ceil(nsm / 128), groups).
 #define IN8_K 128
 template <int MODE> __global__ void __launch_bounds__(256) k_inputs8(const uint8_t* sm8, const pob_sm_exc_t* exc, uint32_t nsm, uint32_t n, int32_t* sm, uint64_t sm_stride, uint32_t s0,
-                                                                      uint32_t w0, uint32_t* bad_wire, uint32_t fault_k, uint32_t fault_g, uint64_t fault_lanes) {
+                                                                      uint32_t w0, uint32_t* bad_wire, uint32_t fault_k, uint32_t fault_g, uint64_t fault_lanes, uint32_t group0) {
     constexpr bool CHECK = MODE == 1;
     int32_t* t = (int32_t*)g_lds;                         // [64 witnesses][IN8_K + 1]
-    const uint32_t tid = threadIdx.x, k0 = blockIdx.x * IN8_K, g = blockIdx.y;
+    const uint32_t tid = threadIdx.x, k0 = blockIdx.x * IN8_K, g = CHECK ? group0 + blockIdx.y : blockIdx.y;
     {   // bytes: thread = (witness row, 32-byte segment)
         const uint32_t row = tid >> 2, seg = tid & 3u, wg = g * 64 + row, kb = k0 + 32 * seg;
         const uint8_t* src = sm8 + (uint64_t)wg * nsm + kb;
@@ -390,6 +391,11 @@ struct pob_ctx {
     // poseidon_wide.hpp PosWideT<true>): pob_constraint_check then runs k_chain_check and collects the records
     bool rode_g = false;
     bool fault_armed = false, fault_g = false; int fault_cls = 0; uint32_t fault_group = 0; uint64_t fault_word = 0, fault_mask = 0;     // pob_debug_store_fault (tests)
+    bool fault_value = false;                             // ... armed by pob_debug_value_fault: the unit goes on with the corrupted value (FAULT_VALUE)
+    // AUDIT (pob_set_audit): every audit_period-th pob_constraint_check whose launches were skipped because the generation rode runs them after all for a window of
+    // audit_groups consecutive groups from audit_cursor -- the independent evaluation of a riding calculator.  audit_tick: checks since pob_set_audit;
+    // audit_first / audit_n: what the last check evaluated (pob_audit_last)
+    uint32_t audit_groups = 0, audit_period = 1, audit_cursor = 0, audit_first = 0, audit_n = 0; uint64_t audit_tick = 0, audit_batches = 0, audit_group_total = 0;
     struct GenLaunch { uint32_t kind, cls, first, count, k_first, k_count; };
     enum { GL_UNITS = 0, GL_CHAIN = 1, GL_POS_CHAIN = 2, GL_ROUNDS = 4 };
     std::vector<GenLaunch> gen_plan[2];
@@ -475,19 +481,19 @@ static void launch_g_emit(const GArgs& A, uint32_t cls, uint32_t nunits, hipStre
     if (cls == 5) launch_g_emit_gm(A, nunits, 1, st); else if (cls == 3) launch_g_emit_sc(A, nunits, 1, st); else if (cls) launch_g_emit_heavy(A, nunits, 1, st); else launch_g_emit_light(A, nunits, 1, st);
 }
 
-static void launch_inputs(pob_ctx* h, int mode, uint32_t G, hipStream_t st) {      // mode: 0 generation, 1 evaluation, 2 generation + its evaluation (k_inputs)
+static void launch_inputs(pob_ctx* h, int mode, uint32_t G, hipStream_t st, uint32_t group0) {      // mode: 0 generation, 1 evaluation (of the groups [group0, group0 + G)), 2 generation + its evaluation (k_inputs)
     if (h->circuit != POB_CIRCUIT_PROOF_OF_BURN || !h->plan.nsm_in) return;
     const SmRef r0 = h->plan.L.pm.numLeafAddressNibbles;  // the small inputs are contiguous SM ranks / wire indices from here (declaration order)
     const uint32_t fk = (mode == 2 && h->fault_armed && !h->fault_g && h->fault_cls == POB_CLASS_SM) ? (uint32_t)h->fault_word - r0.i : 0xFFFFFFFFu;     // pob_debug_store_fault: the input row
     if (h->in_bytes[h->in_cur]) {
         const dim3 grid8((h->plan.nsm_in + IN8_K - 1) / IN8_K, G);
         const size_t lds = 64 * (IN8_K + 1) * 4;
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid8, dim3(256), lds, st, h->d_in_sm8[h->in_cur], h->d_in_exc[h->in_cur], h->plan.nsm_in, h->n, h->d_sm, (uint64_t)h->plan.total.s * 64, r0.i, r0.w, h->d_bad, fk, h->fault_group, h->fault_mask); };
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid8, dim3(256), lds, st, h->d_in_sm8[h->in_cur], h->d_in_exc[h->in_cur], h->plan.nsm_in, h->n, h->d_sm, (uint64_t)h->plan.total.s * 64, r0.i, r0.w, h->d_bad, fk, h->fault_group, h->fault_mask, mode == 1 ? group0 : 0u); };
         if (mode == 1) go(k_inputs8<1>); else if (mode == 2) go(k_inputs8<2>); else go(k_inputs8<0>);
         return;
     }
     const dim3 grid((h->plan.nsm_in + 63) / 64, G);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), 64 * 65 * 4, st, h->d_in_sm[h->in_cur], h->plan.nsm_in, h->d_sm, (uint64_t)h->plan.total.s * 64, r0.i, r0.w, h->d_bad, fk, h->fault_group, h->fault_mask); };
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), 64 * 65 * 4, st, h->d_in_sm[h->in_cur], h->plan.nsm_in, h->d_sm, (uint64_t)h->plan.total.s * 64, r0.i, r0.w, h->d_bad, fk, h->fault_group, h->fault_mask, mode == 1 ? group0 : 0u); };
     if (mode == 1) go(k_inputs<1>); else if (mode == 2) go(k_inputs<2>); else go(k_inputs<0>);
 }
 static Fr limbs_to_mont(const uint64_t* l) {
@@ -1019,7 +1025,7 @@ int pob_generate(pob_handle h, void* stream_) {
         launch_inputs(h, h->gc ? 2 : 0, G, st);
         const bool kf = h->gc && h->fault_armed && !h->fault_g && h->fault_cls == POB_CLASS_BIT;
         const bool gf = ride_g && h->fault_armed && h->fault_g;             // pob_debug_store_fault on a store of a G unit: the riding kernels' FAULT instantiations
-        if (gf) { A.fault_cls = (uint32_t)h->fault_cls; A.fault_group = h->fault_group; A.fault_idx = (uint32_t)h->fault_word; A.fault_lanes = h->fault_mask; }
+        if (gf) { A.fault_cls = (uint32_t)h->fault_cls | (h->fault_value ? FAULT_VALUE : 0u); A.fault_group = h->fault_group; A.fault_idx = (uint32_t)h->fault_word; A.fault_lanes = h->fault_mask; }
         K.fault_group = h->fault_group; K.fault_word = h->fault_word; K.fault_mask = h->fault_mask;
         for (const pob_ctx::GenLaunch& gl : h->gen_plan[h->fused ? 1 : 0]) {
             A.first = gl.first; K.first = gl.k_first;
@@ -1167,12 +1173,31 @@ int pob_constraint_check(pob_handle h, void* stream_) {
             if (h->chk_narrow.count) { A.first = h->chk_narrow.first; launch_g_check_narrow(A, h->chk_narrow.count, G, st); }
             for (const pob_ctx::Seg& sg : h->chk_segs) if (sg.lds != F_MISC && sg.lds != F_RL && sg.lds != F_POS && sg.lds != F_N2B) { A.first = sg.first; launch_g_check(A, sg.lds, sg.count, G, st); }
         }
+        // AUDIT (pob_set_audit): the launches that riding made this check skip, for a window of groups -- the evaluators write their verdicts with atomicMin into the words
+        // the riding launches wrote theirs to, so the records carry the lower of the two.  The window never wraps: one extra launch per kernel.
+        h->audit_first = 0; h->audit_n = rode ? 0 : G;
+        const bool audit_now = rode && h->audit_groups && h->audit_tick % h->audit_period == 0;
+        h->audit_tick++;
+        if (audit_now) {
+            if (h->audit_cursor >= G) h->audit_cursor = 0;           // (a smaller batch than the one the cursor was left in)
+            const uint32_t first = h->audit_cursor, n = std::min(h->audit_groups, G - first);
+            if (!h->plan.sponges.empty()) { KArgs K = kargs(h); K.first = 0; K.group0 = first; launch_k_rounds(K, true, h->nperms, n, st); }
+            launch_inputs(h, 1, n, st, first);
+            if (rode_g) {
+                GArgs W = A; W.group0 = first;
+                if (h->chk_narrow.count) { W.first = h->chk_narrow.first; launch_g_check_narrow(W, h->chk_narrow.count, n, st); }
+                for (const pob_ctx::Seg& sg : h->chk_segs) if (sg.lds != F_MISC && sg.lds != F_RL && sg.lds != F_POS && sg.lds != F_N2B) { W.first = sg.first; launch_g_check(W, sg.lds, sg.count, n, st); }
+            }
+            h->audit_cursor = first + n >= G ? 0 : first + n;
+            h->audit_first = first; h->audit_n = n; h->audit_batches++; h->audit_group_total += n;
+        }
         { int rc = enqueue_collect(h, st, true); if (rc) return rc; }
         HIPC(hipEventRecord(h->ev_check_done, st)); h->check_done_rec = true; h->evaluated = true; h->chk_stream = st; h->chk_ordered = true;
         HIPC(hipEventRecord(h->ev_in_done[h->in_cur], st));
         HIPC(hipGetLastError());
         return POB_OK;
     }
+    h->audit_first = 0; h->audit_n = G; h->audit_tick++;          // (pob_audit_last: the track schedule evaluates every group)
     static const uint32_t side_plan[2][5] = {{F_N2B, F_SC, F_LD, F_RANGE, F_GM}, {F_RL, F_POS, F_MISC, F_SELROW, F_COUNT}};      // (F_GM: gadget-level mains only; F_COUNT: no family)
     // side streams: the generation's (idle during a lone handle's evaluation); in pipeline mode -- the partner generates meanwhile -- the
     // pool's two evaluation streams
@@ -1230,6 +1255,23 @@ int pob_set_inorder(pob_handle h, int on) {
     if (!h) return POB_E_ARG;
     if (on && h->partner) { h->err = "an in-order calculator has no partner: unlink first (pob_set_partner(h, NULL))"; return POB_E_STATE; }
     h->inorder = on != 0; h->fused = (on & 2) != 0; h->gc = (on & 4) != 0;
+    return POB_OK;
+}
+
+int pob_set_audit(pob_handle h, uint32_t groups, uint32_t period) {
+    if (!h) return POB_E_ARG;
+    if (groups && !period) { h->err = "pob_set_audit: period 0 (audit every period-th check; 1 = every check)"; return POB_E_ARG; }
+    h->audit_groups = groups; h->audit_period = period ? period : 1;
+    h->audit_cursor = 0; h->audit_tick = 0; h->audit_batches = 0; h->audit_group_total = 0;
+    return POB_OK;
+}
+
+int pob_audit_last(pob_handle h, uint32_t* first_group, uint32_t* n_groups, uint64_t* audited_batches, uint64_t* audited_groups) {
+    if (!h) return POB_E_ARG;
+    if (first_group) *first_group = h->audit_first;
+    if (n_groups) *n_groups = h->audit_n;
+    if (audited_batches) *audited_batches = h->audit_batches;
+    if (audited_groups) *audited_groups = h->audit_group_total;
     return POB_OK;
 }
 
@@ -2383,7 +2425,46 @@ int pob_debug_store_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
         }
         if (wire) *wire = 0xFFFFFFFFu;
     }
-    h->fault_armed = true; h->fault_cls = cls; h->fault_group = group; h->fault_word = index; h->fault_mask = mask;
+    h->fault_armed = true; h->fault_value = false; h->fault_cls = cls; h->fault_group = group; h->fault_word = index; h->fault_mask = mask;
+    return POB_OK;
+}
+
+int pob_debug_value_fault(pob_handle h, int cls, uint32_t group, uint64_t index, uint64_t mask, uint32_t* wire) {
+    if (!h || group >= h->groups) return POB_E_ARG;
+    if (!h->inorder || !h->gc) { h->err = "pob_debug_value_fault: the calculator's generation carries no evaluation (pob_set_inorder bit 2)"; return POB_E_STATE; }
+    const Cur t = h->plan.total;
+    if (!(cls == POB_CLASS_BIT ? index < t.b : cls == POB_CLASS_SM ? index < t.s : cls == POB_CLASS_FR ? index < t.f : false)) { h->err = "pob_debug_value_fault: no such word"; return POB_E_ARG; }
+    auto refuse = [&](const char* why) { h->err = std::string("pob_debug_value_fault: not covered: ") + why; return POB_E_ARG; };
+    if (!(h->circuit == POB_CIRCUIT_PROOF_OF_BURN || h->circuit == POB_CIRCUIT_SPEND)) return refuse("the G units of a gadget-level main do not ride");
+    if (cls == POB_CLASS_BIT) return refuse("BIT words (round blocks, sponge chains, the G units' bit runs)");
+    if (cls == POB_CLASS_SM && h->circuit == POB_CIRCUIT_PROOF_OF_BURN) {
+        const SmRef r0 = h->plan.L.pm.numLeafAddressNibbles;
+        if (index >= r0.i && index < r0.i + h->plan.nsm_in) return refuse("an input row (stored from the packed inputs, no unit computes it)");
+    }
+    uint32_t w = 0xFFFFFFFFu;
+    bool in_block = false;
+    if (cls == POB_CLASS_FR) for (const UnitDesc& d : h->plan.units) if (d.kind == U_POS_WIDE) {      // an element of a lane-spread Poseidon block
+        const int T = (int)d.a[0];
+        if (index < d.cur.f || index >= (uint64_t)d.cur.f + pos_wires(T, pos_off(T).rp)) continue;
+        if (!posw_value_fault_covers(T, (uint32_t)(index - d.cur.f))) return refuse("an element of a Poseidon block that does not carry the running state (Sigma internals, operand copies)");
+        w = d.cur.w + (uint32_t)(index - d.cur.f); in_block = true;
+    }
+    if (!in_block) {
+        // a put of a G unit: the generating unit is the one whose wires begin last at or before the rank (units are recorded where their wires begin).  The RLP units generate on
+        // the plain policy inside the riding kernel (circuits.hpp unit_run_ride), which has no FAULT form.  Whether a unit stores the word at all is not known here (as for
+        // pob_debug_store_fault): a rank that no riding put writes arms nothing
+        uint64_t best = 0; bool any = false, rl = false;
+        for (const UnitDesc& d : h->plan.units) if ((d.flags & UNIT_GEN) && d.kind != U_POS_WIDE) {
+            const uint64_t s = cls == POB_CLASS_SM ? d.cur.s : d.cur.f;
+            if (s > index) continue;
+            if (!any || s > best) { best = s; any = true; rl = false; }
+            if (s == best && ride_keeps_evaluation(d.kind)) rl = true;
+        }
+        if (rl) return refuse("a wire of the RLP units, which generate on the plain policy");
+    }
+    if (wire) *wire = w;
+    if (mask == 0) { if (h->fault_value) h->fault_armed = false; return POB_OK; }      // (disarms a value fault only -- a pending pob_debug_store_fault stays armed, so the call serves as a coverage probe; the answer above still says whether the word is covered)
+    h->fault_g = true; h->fault_armed = true; h->fault_value = true; h->fault_cls = cls; h->fault_group = group; h->fault_word = index; h->fault_mask = mask;
     return POB_OK;
 }
 

@@ -297,7 +297,7 @@ struct DevMem {
     const int32_t* in_sm;     //                              SM inputs [64 lanes][nsm]
     uint32_t nfr_in, nsm_in, npow256;
     uint32_t lane;
-    uint32_t fault_cls, fault_idx; uint64_t fault_lanes;      // GenPT<true, true> (tests, pob_debug_store_fault): the store of storage class / rank reaches memory corrupted for these witnesses
+    uint32_t fault_cls, fault_idx; uint64_t fault_lanes;      // GenPT<true, true> (tests, pob_debug_store_fault / pob_debug_value_fault): the store of storage class / rank reaches memory corrupted for these witnesses
     // buffer resources over the three slabs: a wire access is `buffer_load/store v, v_lane_offset, s[rsrc], s_wire_offset offen`
     // -- the per-wire part of the address stays scalar, no 64-bit per-lane address arithmetic (or registers) per access
     __amdgpu_buffer_rsrc_t rs_bits, rs_sm, rs_fr;
@@ -419,7 +419,11 @@ struct DevPol : PolBase {
 template <bool RIDE, bool FAULT = false> struct GenPT : DevPol {
     static constexpr bool is_gen = true, is_check = false, is_emit = false, is_count = false, ride = RIDE;
     // FAULT (tests): what goes to memory for the armed (class, rank): bit 0 of the value flipped for the witnesses of fault_lanes -- the unit goes on with the right value
-    __device__ __forceinline__ bool hit(uint32_t cls, uint32_t i) const { return FAULT && m.fault_cls == cls && m.fault_idx == i; }
+    // (pob_debug_store_fault: the load-back differs) or, fault_cls | 0x100 (pob_debug_value_fault, SM and FR puts), with the corrupted one: the VALUE is wrong before the store, the
+    // load-back agrees with it and only an evaluation that recomputes the wire from its stored operands can tell
+    __device__ __forceinline__ bool hit(uint32_t cls, uint32_t i) const { return FAULT && (m.fault_cls & 0xFFu) == cls && m.fault_idx == i; }
+    __device__ __forceinline__ bool hit_store(uint32_t cls, uint32_t i) const { return hit(cls, i) && !(m.fault_cls & 0x100u); }
+    __device__ __forceinline__ bool hit_value(uint32_t cls, uint32_t i) const { return hit(cls, i) && (m.fault_cls & 0x100u) && ((m.fault_lanes >> m.lane) & 1); }
     uint32_t status;   // this lane's first failing assert (0 = none yet)
     // RIDE: lowest wire whose loaded value differs from the value stored (per lane), and the one pending compare per class
     uint32_t bad_wire;
@@ -437,17 +441,25 @@ template <bool RIDE, bool FAULT = false> struct GenPT : DevPol {
         ps_l = ps_v = 0; pb_l = pb_v = 0; pr_l = pr_x = 0;
     }
     __device__ __forceinline__ B put(BitRef r, B v) {
-        st(r, hit(0, r.i) ? v ^ m.fault_lanes : v);
+        st(r, hit_store(0, r.i) ? v ^ m.fault_lanes : v);
         if constexpr (RIDE) { const B l = run_ld_off(POB_UNI(r.i) << 3); POB_RIDE_BARRIER(); res_b(); pb_l = l; pb_v = v; pb_w = r.w; }
         return v;
     }
     __device__ __forceinline__ S put(SmRef r, S v) {
-        st(r, (hit(1, r.i) && ((m.fault_lanes >> m.lane) & 1)) ? v ^ 1 : v);
+        if constexpr (FAULT) { if (hit_value(1, r.i)) v ^= 1; }
+        st(r, (hit_store(1, r.i) && ((m.fault_lanes >> m.lane) & 1)) ? v ^ 1 : v);
         if constexpr (RIDE) { const S l = ld(r); POB_RIDE_BARRIER(); res_s(); ps_l = l; ps_v = v; ps_w = r.w; }
         return v;
     }
     __device__ __forceinline__ F put(FrRef r, const F& v) {
-        if (hit(2, r.i) && ((m.fault_lanes >> m.lane) & 1)) { F w = v; w.l[0] ^= 1u; st(r, w); } else st(r, v);
+        if constexpr (FAULT) {
+            if (hit_value(2, r.i)) {          // the unit goes on with the corrupted element: stored, loaded back and returned
+                F w = v; w.l[0] ^= 1u; st(r, w);
+                if constexpr (RIDE) { const F l = ld(r); mark(!fr_eq(l, w), r.w); POB_OPAQUE(bad_wire); }
+                return w;
+            }
+        }
+        if (hit_store(2, r.i) && ((m.fault_lanes >> m.lane) & 1)) { F w = v; w.l[0] ^= 1u; st(r, w); } else st(r, v);
         if constexpr (RIDE) {
             const F l = ld(r); mark(!fr_eq(l, v), r.w); POB_OPAQUE(bad_wire);      // (resolved at once: a pending field element is 16 VGPRs the kernel does not have at four wavefronts per SIMD)
         }
@@ -460,7 +472,7 @@ template <bool RIDE, bool FAULT = false> struct GenPT : DevPol {
     __device__ __forceinline__ void require(B ok, uint32_t code) { if (!bit(ok) && status == 0) status = code; }
     __device__ __forceinline__ void require_lane(bool ok, uint32_t code) { if (!ok && status == 0) status = code; }
     __device__ __forceinline__ void run_put(uint32_t n, uint32_t w, uint32_t i, B x) {
-        const B xs = hit(0, i) ? x ^ m.fault_lanes : x;       // (i: this lane's BIT rank)
+        const B xs = hit_store(0, i) ? x ^ m.fault_lanes : x;       // (i: this lane's BIT rank)
         pob_v2i q; q.x = (int)(uint32_t)xs; q.y = (int)(uint32_t)(xs >> 32);
         const uint32_t off = run_off(n, i);
         __builtin_amdgcn_raw_buffer_store_b64(q, m.rs_bits, (int)off, 0, 0);

@@ -39,6 +39,8 @@ template <bool RIDE, bool FAULT = false> struct PosWideT {
     uint32_t w_also;               // ... of the caller's copy of the hash (outside the block): reported at the block's first wire
     mutable Fr pl, pv; mutable uint32_t pw, bad;      // RIDE: the pending compare (loaded, stored, wire) and the lowest wire that differed
     uint32_t fault_f; bool fault_me;                  // FAULT (tests, pob_debug_store_fault): FR rank whose store reaches memory with bit 0 flipped, for this lane's witness
+    bool fault_val;                                   // ... pob_debug_value_fault: the element is wrong BEFORE the store -- the load-back agrees, st() returns it and the block goes on with it
+                                                      //     where the stored element is the running state (posw_value_fault_covers)
     __device__ __forceinline__ void ride_init() { pl = pv = fr_zero(); pw = 0; bad = 0xFFFFFFFFu; }
     __device__ __forceinline__ void ride_resolve() const { if (!fr_eq(pl, pv) && pw < bad) bad = pw; POB_OPAQUE(bad); }
     __device__ __forceinline__ Fr ld(uint32_t f) const {
@@ -47,9 +49,12 @@ template <bool RIDE, bool FAULT = false> struct PosWideT {
         for (int k = 0; k < 8; k++) v.l[k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(off + 256u * k), 0, 0);
         return v;
     }
-    __device__ __forceinline__ void st(bool on, uint32_t f, const Fr& v, bool also = false) const {
+    // -> the element the block goes on with: v (FAULT, a value fault armed on this element: v with bit 0 flipped)
+    __device__ __forceinline__ Fr st(bool on, uint32_t f, const Fr& v_in, bool also = false) const {
         const uint32_t off = on ? (f << 11) + slot4 : 0xFFFFF000u;              // off: past the slab, dropped
-        const uint32_t flip = (FAULT && fault_me && f == fault_f) ? 1u : 0u;
+        Fr v = v_in;
+        if constexpr (FAULT) { if (fault_val && fault_me && on && f == fault_f) v.l[0] ^= 1u; }
+        const uint32_t flip = (FAULT && !fault_val && fault_me && f == fault_f) ? 1u : 0u;
 #pragma unroll
         for (int k = 0; k < 8; k++) __builtin_amdgcn_raw_buffer_store_b32((int)(k == 0 ? v.l[0] ^ flip : v.l[k]), rs, (int)(off + 256u * k), 0, 0);
         if constexpr (RIDE) {
@@ -60,6 +65,7 @@ template <bool RIDE, bool FAULT = false> struct PosWideT {
             ride_resolve();
             pl = l; pv = fr_sel(on, v, fr_zero()); pw = also ? w_also : f + w_of_f;   // (... and expects 0)
         }
+        return v;
     }
     __device__ __forceinline__ Fr kc(uint32_t idx) const {                      // table constant (per-lane index)
         Fr v; const uint32_t* q = ktab + (size_t)(idx - kbase) * 8;
@@ -106,8 +112,8 @@ template <int T, class PW> __device__ __forceinline__ Fr posw_sbox(const PW& W, 
     const Fr x2 = fr_sqr_inl(x), x4 = fr_sqr_inl(x2), x5 = fr_mul_inl(x4, x);
     const uint32_t sg = off + 4 * e;
     W.st(act, sg + 1, x); W.st(act, sg + 2, x2); W.st(act, sg + 3, x4); W.st(act, sg, x5);
-    const Fr y = fr_add(x5, W.kc(cr + (act ? e : 0)));
-    W.st(act, off + 5 * T + e, x5); W.st(act, off + 4 * T + e, y);
+    Fr y = fr_add(x5, W.kc(cr + (act ? e : 0)));
+    W.st(act, off + 5 * T + e, x5); y = W.st(act, off + 4 * T + e, y);         // Ark.out: what Mix reads
     W.st(act, off + 7 * T + e, y);
     return y;
 }
@@ -130,11 +136,9 @@ template <int T, class PW> __device__ __forceinline__ void posw_full(const PW& W
         const Fr yi = posw_from(yb, g0 | 1u);
         acc = fr_add(acc, fr_mul_inl(W.kc(mat + jc * T + 4), yi));
         accb = fr_add(accb, fr_mul_inl(W.kc(mat + 4 * T + 4), yi));
-        W.st(actb, off + 6 * T + 4, accb);
-        xb = accb;
+        xb = W.st(actb, off + 6 * T + 4, accb);                                 // Mix.out: the next round's input
     }
-    W.st(act, off + 6 * T + j, acc);
-    x = acc;
+    x = W.st(act, off + 6 * T + j, acc);
 }
 
 template <int T, class PW> __device__ __forceinline__ void posw_run(const GArgs& A, const PosWDesc& d, const PW& W, uint32_t lane) {
@@ -149,12 +153,12 @@ template <int T, class PW> __device__ __forceinline__ void posw_run(const GArgs&
     W.st(act && l0, base + 2 * T, x);                            // initialState = 0
     W.st(act, base + 3 * T + 1 + j, x);                          // Ark0.in
     x = fr_add(x, W.kc(k.C + jc));
-    W.st(act, base + 2 * T + 1 + j, x);                          // Ark0.out
+    x = W.st(act, base + 2 * T + 1 + j, x);                      // Ark0.out
     if constexpr (T == 5) {
         xb = posw_input<T>(A, d, W, 4, actb);
         W.st(actb, base + 4, xb); W.st(actb, base + T + 4, xb); W.st(actb, base + 3 * T + 5, xb);
         xb = fr_add(xb, W.kc(k.C + 4));
-        W.st(actb, base + 2 * T + 5, xb);
+        xb = W.st(actb, base + 2 * T + 5, xb);
     }
     uint32_t off = base + 4 * T + 1;
     // ---- 4 full rounds (the fourth mixes with P)
@@ -178,7 +182,7 @@ template <int T, class PW> __device__ __forceinline__ void posw_run(const GArgs&
         if constexpr (T == 5) {
             const Fr cp = W.kc(r ? sb - (2 * T - 1) + T + 3 : sb);
             m2 = fr_mul_inl(fr_sel(l0, m1, pin0), fr_sel(l0, m1, cp));           // x^4 | in_0' * S'_4'
-            if (r) { xb = fr_add(xb, m2); W.st(actb, poff + 4 + 4, xb); }
+            if (r) { xb = fr_add(xb, m2); xb = W.st(actb, poff + 4 + 4, xb); }
             m3 = fr_mul_inl(fr_sel(l0, m2, xb), fr_sel(l0, x, W.kc(sb + 4)));    // x^5 | S_4 * x_4
         } else {
             m2 = fr_sqr_inl(m1);                                     // x^4 (lane 0 only)
@@ -196,13 +200,13 @@ template <int T, class PW> __device__ __forceinline__ void posw_run(const GArgs&
         if (!act) part = fr_zero();
         const Fr sum = posw_group_sum(part, lane);
         x = fr_sel(l0, sum, fr_add(x, m4));
-        W.st(act, off + 4 + j, x);
+        x = W.st(act, off + 4 + j, x);                               // MixS.out
         if constexpr (T == 5) { pin0 = in0; poff = off; }
         off += 4 + 2 * T;
     }
     if constexpr (T == 5) {                                      // the last round's deferred in_0 * S'_4
         xb = fr_add(xb, fr_mul_inl(pin0, W.kc(k.S + (2 * T - 1) * (k.rp - 1) + T + 3)));
-        W.st(actb, poff + 4 + 4, xb);
+        xb = W.st(actb, poff + 4 + 4, xb);
     }
     // ---- 3 full rounds
 #pragma unroll 1
@@ -230,6 +234,7 @@ template <int T, class PW> __device__ __forceinline__ void posw_run(const GArgs&
     }
 }
 
+// (which elements a value fault may be armed on -- where posw_run assigns what st() returns: circuits.hpp posw_value_fault_covers)
 // bx = 4 * unit + witness slice (unit = position in the launch's list), g = group; the wavefronts of a workgroup have the same unit
 #define POSW_SLICES 4              // wavefronts per (unit, group): 16 witnesses each
 #ifndef POSW_WAVES
@@ -257,7 +262,7 @@ template <bool RIDE, bool FAULT = false> __device__ __forceinline__ void poswide
     W.ktab = g_lds; W.kbase = k.C;
     W.w_of_f = POB_UNI(dp->cur.w) - d.base; W.w_also = POB_UNI(dp->cur.w);
     if constexpr (RIDE) W.ride_init();
-    if constexpr (FAULT) { W.fault_f = A.fault_idx; W.fault_me = A.fault_cls == 2 && g == A.fault_group && ((A.fault_lanes >> slot) & 1); }
+    if constexpr (FAULT) { W.fault_f = A.fault_idx; W.fault_me = (A.fault_cls & 0xFFu) == 2 && g == A.fault_group && ((A.fault_lanes >> slot) & 1); W.fault_val = (A.fault_cls & FAULT_VALUE) != 0; }
     if (T == 3) posw_run<3>(A, d, W, lane); else if (T == 4) posw_run<4>(A, d, W, lane); else posw_run<5>(A, d, W, lane);
     if constexpr (RIDE) {          // the last pending compare; the lowest differing wire over the 4 lanes of a witness, reported by its first lane
         W.ride_resolve();

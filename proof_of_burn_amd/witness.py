@@ -203,6 +203,12 @@ def load_library() -> ctypes.CDLL:
     lib.pob_probe_check_kernel.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     lib.pob_debug_xor_bits.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
     lib.pob_debug_store_fault.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]
+    # (absent in an older build named by POB_LIB_PATH: tools/audit_cost.py --parent, which never calls them on that build.  That a CURRENT build has the three exports is enforced by
+    #  EXPORTED_SYMBOLS, which build() resolves one by one, not here: on a library without them set_audit / audit_last / value_fault fail with ctypes' AttributeError)
+    if hasattr(lib, "pob_set_audit"):
+        lib.pob_set_audit.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+        lib.pob_audit_last.argtypes = [vp, u32p, u32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        lib.pob_debug_value_fault.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]
     lib.pob_debug_poke.argtypes = [vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
     lib.pob_debug_emit_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.pob_emit_selfcheck.argtypes = [vp, ctypes.c_int]
@@ -226,7 +232,7 @@ EXPORTED_SYMBOLS = ["pob_plan_info", "pob_gadget_template", "pob_open", "pob_clo
                     "pob_upload_inputs8", "pob_upload_inputs8_async", "pob_narrow_inputs", "pob_pack_json_batch8",
                     "pob_results_fetch", "pob_results_wait", "pob_emit_begin_reduced", "pob_reduced_map_pin", "pob_write_wtns_reduced", "pob_emit_measure_ex", "pob_generate",
                     "pob_constraint_check", "pob_sync", "pob_set_partner", "pob_results", "pob_results_device", "pob_results_records_device", "pob_gather_records", "pob_emit_witness",
-                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_emit_group_selfcheck", "pob_emit_group_selfcheck_result", "pob_debug_selfcheck_sites", "pob_debug_group_emit_xor", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
+                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_emit_group_selfcheck", "pob_emit_group_selfcheck_result", "pob_debug_selfcheck_sites", "pob_debug_group_emit_xor", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_set_audit", "pob_audit_last", "pob_debug_value_fault", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
 
 
 def plan_info(main: str) -> PobInfo:
@@ -778,6 +784,18 @@ class WitnessCalculator:
         constraint_check skips its round kernel unless a debug poke touched the vector in between"""
         self._ck(self.lib.pob_set_inorder(self.h, int(on)))
 
+    def set_audit(self, groups: int, period: int = 1):
+        """the independent evaluation of a riding calculator (pob_set_audit): every period-th constraint_check that skipped launches because the generation rode
+        (set_inorder(... | 4)) runs them for a window of `groups` consecutive groups of 64 witnesses, the window moving on by its size per audited batch; 0 = off"""
+        self._ck(self.lib.pob_set_audit(self.h, int(groups), int(period)))
+
+    def audit_last(self) -> dict:
+        """what the last constraint_check evaluated independently (pob_audit_last): n_groups = 0: nothing; (0, G): every group anyway; else the audit window -- and the
+        totals of window audits since set_audit"""
+        f, n, b, g = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._ck(self.lib.pob_audit_last(self.h, ctypes.byref(f), ctypes.byref(n), ctypes.byref(b), ctypes.byref(g)))
+        return {"first_group": int(f.value), "n_groups": int(n.value), "audited_batches": int(b.value), "audited_groups": int(g.value)}
+
     def emit_selfcheck(self, enable: bool = True):
         """every following emission (O0 or reduced) evaluates the derived wires' own relations on the values written into its windows (pob_emit_selfcheck)"""
         self._ck(self.lib.pob_emit_selfcheck(self.h, 1 if enable else 0))
@@ -1007,6 +1025,18 @@ class WitnessCalculator:
         w = ctypes.c_uint32()
         rc = self.lib.pob_debug_store_fault(self.h, cls, group, index, lane_mask, ctypes.byref(w))
         if rc == -1 and "not a stored word" in self.lib.pob_strerror(self.h).decode():
+            return None
+        self._ck(rc)
+        return int(w.value)
+
+    def value_fault(self, index: int, lane_mask: int, group: int = 0, cls: int = 2):
+        """arm ONE fault of the generator in the next generation (pob_debug_value_fault; calculators with set_inorder(... | 4)): the SM value / FR element of storage class cls
+        at rank `index` is computed wrong (bit 0 flipped) for the witnesses of lane_mask and the unit goes on with it, so the riding verdict stays clean.  Returns the O0 wire of
+        the word where the library knows it (an element of a Poseidon block), UNKNOWN_WIRE for a put of a G unit (if a riding unit stores the word at all), or None for a
+        word the hook does not cover (BIT words, input rows, the RLP units' wires, the Poseidon elements that do not carry the running state).  lane_mask = 0 disarms."""
+        w = ctypes.c_uint32()
+        rc = self.lib.pob_debug_value_fault(self.h, cls, group, index, lane_mask, ctypes.byref(w))
+        if rc == -1 and "not covered" in self.lib.pob_strerror(self.h).decode():
             return None
         self._ck(rc)
         return int(w.value)

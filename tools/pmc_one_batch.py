@@ -14,6 +14,8 @@ batch = gen.synthetic_batch(NB, depth=10, seed=0xB0B, distinct_keys=16)
 calc = WitnessCalculator(MAIN, max_batch=NB)
 if os.environ.get("POB_PMC_INORDER", "7") != "0":
     calc.set_inorder(int(os.environ.get("POB_PMC_INORDER", "7")))          # 7: the schedule bench.py runs (in order, fused launch, evaluation riding with the generation); 3 / 1: without
+if os.environ.get("POB_PMC_AUDIT"):
+    calc.set_audit(int(os.environ["POB_PMC_AUDIT"]))                      # the audit's extra launches for a window of that many groups (pob_set_audit; the second pass: the window behind the first one's)
 for _ in range(2):
     res = calc.calculate(batch.inputs, check=True)
     assert all(r.ok and r.check_status == 0 for r in res)
