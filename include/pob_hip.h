@@ -24,7 +24,8 @@ enum { POB_OK = 0, POB_E_ARG = -1, POB_E_HIP = -2, POB_E_NOMEM = -3, POB_E_STATE
 
 typedef struct {
     uint64_t n_witness;          /* W: O0 wires incl. the constant-1 wire (= nWitness of the .wtns)            */
-    uint64_t n_bit, n_sm, n_fr;  /* STORED wires per storage class (policy.hpp); n_bit + n_sm + n_fr + n_derived + n_alias + 1 = n_witness */
+    uint64_t n_bit, n_sm, n_fr;  /* STORED wires per storage class (policy.hpp); n_bit + n_sm + n_fr + n_derived + n_alias + 1 = n_witness.  n_bit COUNTS wires: the
+                                    BIT slab of a group is bit_stride words (below), and the ranks the debug entry points take run over [0, bit_stride)            */
     uint32_t n_fr_inputs, n_sm_inputs, n_outputs;
     uint32_t n_units, n_sponges, n_perms, n_stages, max_batch;
     uint64_t group_bytes;        /* HBM-resident bytes of the compact witness vector per 64 witnesses           */
@@ -51,6 +52,11 @@ typedef struct {
                                     input -- (101 k + 25) / k arrays of 512 B per (64 witnesses, round)                                               */
     uint32_t kgc_rounds;         /* ... that one wavefront of the launch which expands AND evaluates the round blocks covers (k_rounds_gc, pob_set_inorder bit 2): per round
                                     76 arrays stored and loaded back + the 25 of the stored midRound[r+1], midRound[r0] once                             */
+    uint64_t bit_stride;         /* 8-byte words between two groups' BIT slabs: n_bit + the PADDING words that put every sponge's stored region and every
+                                    KeccakBytes.inBlocks array on a 128-byte line (a BIT rank that is a multiple of 16), itself a multiple of 16 -- so that every
+                                    512-byte row the sponge kernels store and load covers four whole lines in every group.  Padding words belong to no wire and
+                                    no kernel touches them: pob_debug_store_fault answers 0xFFFFFFFF for them, pob_debug_ref("bit.pad", k) lists the runs.
+                                    group_bytes counts them                                                                                              */
 } pob_info_t;
 
 /* Replaces `component main = ProofOfBurn(...)` / `Spend(...)` + circom -c + make (reference
@@ -416,7 +422,7 @@ int pob_debug_fr_inv(int device, const uint8_t* in, uint32_t n, uint8_t* out_kal
 int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr, uint8_t* out_mul);
 /* Test hook: storage class, rank within the class and wire index of a few named wires: "commitment"; "poseidon" (k-th wire of the
  * first Poseidon block), "poseidon.t3" / ".t4" / ".t5" (... of the first Poseidon block of width T = 3 / 4 / 5); "pad.div.out" / "pad.div.rem" of KeccakBytes instance k (the Divide hint of divide.circom:23-24); ProofOfBurn only: "sc.exists" [k] of layer 1's SubstringCheck. */
-int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k; "kb.inBlocks": its first inBlocks bit; "kb.absorb": the first stored word (midRound[0][0][0]) and the first wire of its first Absorb block */
+int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k; "kb.inBlocks": its first inBlocks bit; "kb.absorb": the first stored word (midRound[0][0][0]) and the first wire of its first Absorb block; "bit.pad": the k-th run of padding words of the BIT slab (pob_info_t.bit_stride), *index = its first rank, *wire = its length in words */
 
 /* Host helper used by the input producers (next row f1): Keccak-256 of a byte string.                           */
 void pob_keccak256(const uint8_t* msg, uint64_t len, uint8_t out[32]);

@@ -158,6 +158,8 @@ struct UnitDesc { uint32_t kind, stage; Cur cur; uint32_t a[8]; uint32_t cost, f
 
 #define SC_RANGE_POS 32          // positions of SubstringCheck's existence loop per unit (one batch inversion each; <= 64: the zero flags are one 64-bit word).  64 measured: generation 1.07 -> 1.00 ms alone, evaluation 0.40 -> 0.57 ms
 #define MAX_KB 72
+static_assert(BIT_PAD_MAX >= 2 * MAX_KB + 1, "two padding runs per KeccakBytes instance and the slab's end");
+static_assert(ABSORB_BITS % BIT_ALIGN == 0 && AB_DIRECT % BIT_ALIGN == 0 && KR_BITS % BIT_ALIGN == 0 && 1600u % BIT_ALIGN == 0 && 1088u % BIT_ALIGN == 0, "every offset inside a sponge keeps the line alignment of its first word");
 #define MAX_SC 64
 // everything a unit body needs besides the policy; lives in device memory, read-only on the device
 struct CircuitLayout {
@@ -209,6 +211,7 @@ HD bool posw_value_fault_covers(int T, uint32_t rel) {
 //    || Divide(16)(inLen,136), AssertLessEqThan(16)(numBlocks, mb), IsEqual([i,inLen]) x m, IsEqual([i,numBlocks*136-1]) x m
 // || Num2Bits(8) x m, Flatten(m,8), Keccak(mb), Reshape(32,8), Bits2Num(8) x 32
 #define NO_RANK 0xFFFFFFFFu
+#define KB_HEAD_TAIL_BITS 251u     // stored BIT wires of Pad's Divide(16) + AssertLessEqThan(16): 167 + 84 (kb_head)
 template <class P> HD BitRef dbits(P& p, uint32_t n) { BitRef r = {p.dvs(n), NO_RANK}; return r; }      // n DERIVED BIT wires: wire indices only
 template <class P> GD void kb_head(P& p, int mb, S inLen, KBRefs& r) {
     const uint32_t m = 136 * mb;
@@ -217,11 +220,16 @@ template <class P> GD void kb_head(P& p, int mb, S inLen, KBRefs& r) {
     // the padded bytes' bits exist six times in the circuit (Num2Bits(8).out, inBitsArray, Flatten in / out, inBits, inBlocks): stored ONCE, as inBlocks (the sponge's
     // source); the hash bits ten times (Selector.out, SelectorArray2D.out, Final.out, Keccak.finalState / out, outBits, Reshape in / out, outBytes, Bits2Num.in): stored
     // once, as Selector.out.  The copies are derived wires (policy.hpp run_derived).
-    r.inBitsArray = dbits(p, 8 * m); r.inBits = dbits(p, 8 * m); r.inBlocks = p.bits(8 * m); r.outBits = dbits(p, 256); r.outBytes = dbits(p, 256);
+    // (inBlocks is what the sponge chain reads as 512-byte rows, 1 088 words per block: it starts on a 128-byte line, policy.hpp align_bits)
+    r.inBitsArray = dbits(p, 8 * m); r.inBits = dbits(p, 8 * m); p.align_bits(); r.inBlocks = p.bits(8 * m); r.outBits = dbits(p, 256); r.outBytes = dbits(p, 256);
     inLen = p.put(r.inLen, inLen);
     gAssertLessThanS(p, 16, inLen, (S)m);
     r.pad_o_w = p.dvs(m); r.pad_nb = p.sms(1); r.pad_in_w = p.dvs(m); r.pad_il = p.sms(1); r.pad_dv = p.sms(1); r.pad_rm = p.sms(1);
     r.pad_flt = p.bits(m + 1); r.pad_isEq = p.bits(m); r.pad_isLast = p.bits(m);
+    // the padding that puts the sponge's stored region (kb_declare_keccak: abs_b) on a 128-byte line is taken HERE, KB_HEAD_TAIL_BITS ranks ahead of it -- the BIT wires of
+    // Divide(16) and AssertLessEqThan(16) below, the only ones between this point and the sponge; the planner checks the figure (Plan::keccak_tail).  Why not directly ahead of
+    // the region: DESIGN.md 2 (a padding word is a rank below n_bit that no evaluation can flag, and the seeded corruption sweeps draw their ranks from [0, n_bit))
+    p.align_bits(KB_HEAD_TAIL_BITS);
     inLen = p.put(r.pad_il, inLen);
     S q, rem;
     r.c_div = p.cur;
@@ -329,6 +337,9 @@ template <class P> GD void kb_declare_keccak(P& p, KBRefs& r) {
     // (Keccak.in / Final.in: copies of KeccakBytes.inBlocks; Final.s[0] = 0, Final.s[k + 1] = Absorb k's output = its midRound[24]: derived, expanded by the emitter from those words)
     r.k_out = dbits(p, 256); r.k_in = dbits(p, n * 1088); r.k_blocks = p.sms(1); r.k_finalState = dbits(p, 1600);
     r.f_out = dbits(p, 1600); r.f_in = dbits(p, n * 1088); r.f_blocks = p.sms(1); r.f_s = dbits(p, (n + 1) * 1600);
+    // the sponge's stored region starts on a 128-byte line: every offset inside it (ABSORB_BITS, AB_DIRECT, KR_BITS, a state, an array) is a multiple of 16 words, so
+    // every 512-byte row the chain and round kernels store and load covers four whole lines.  (kb_head has padded for it already: nothing is left to skip here)
+    p.align_bits();
     r.abs_w = p.cur.w; r.abs_b = p.cur.b;
     p.skip_alias(n * ABSORB_WIRES, n * ABSORB_BITS);
     r.sel_out = dbits(p, 1600); r.sel_arrays = dbits(p, (n + 1) * 1600); r.sel_select = p.sms(1); r.sel_T = dbits(p, 1600 * (n + 1));      // (copies of Selector.out / of Final.s: derived)
@@ -1087,7 +1098,11 @@ struct Plan {
     CircuitLayout L;
     std::vector<UnitDesc> units;
     std::vector<SpongeDesc> sponges;
-    Cur total;            // = counts (total.w = nWitness)
+    Cur total;            // = counts (total.w = nWitness; total.b = STORED BIT wires, the padding not counted)
+    // BIT words between two groups' slabs: total.b + the padding words (policy.hpp align_bits), itself a multiple of BIT_ALIGN -- and of nothing coarser: a power-of-two
+    // stride would put every group's rows on the same memory channels.  Whatever sizes the slab or steps from group to group uses the stride; total.b only counts.
+    uint32_t bit_stride;
+    PadLog pads;          // the padding runs, in rank order (pob_debug_ref "bit.pad")
     uint32_t nfr_in, nsm_in, max_stage;
     // Side tracks: stage ids TRACK_STRIDE*t + s belong to track t.  Track 0 is the main sequence; track t > 0 starts once stage
     // track_fork[t] has completed and must have completed before stage track_join[t] starts.  A track may only be joined by a
@@ -1166,6 +1181,7 @@ struct Plan {
     void keccak_tail(uint32_t kb, uint32_t range_stage, SmRef dst, bool has_dst) {
         KBRefs& r = L.kbs[kb];
         r.index = kb;
+        if (p.cur.b % BIT_ALIGN) throw std::runtime_error("layout planner: KB_HEAD_TAIL_BITS is not the BIT footprint between kb_head's padding step and the sponge");
         kb_declare_keccak(p, r);
         SpongeDesc s; s.n = r.mb; s.stage = range_stage + 1; s.src_b = r.inBlocks.i; s.src_w = r.inBlocks.w;
         s.kin_w = r.k_in.w; s.fin_w = r.f_in.w; s.fs_w = r.f_s.w; s.abs_b = r.abs_b; s.abs_w = r.abs_w;
@@ -1259,8 +1275,19 @@ struct Plan {
             CountP q; const UnitDesc dd = d; unit_run_all(q, dd, L); d.cost = q.nput * (unit_is_heavy(d.kind) ? 4 : 1);
         }
     }
+    // every plan_*: the walk's padding runs are logged from begin() on; finish() closes the slab on a line and separates the count from the stride
+    void begin() { memset(&pads, 0, sizeof pads); p.pads = &pads; }
+    void finish() {
+        p.align_bits();
+        p.pads = nullptr;
+        if (pads.n > BIT_PAD_MAX) throw std::runtime_error("layout planner: more padding runs than BIT_PAD_MAX");
+        bit_stride = p.cur.b;
+        total = p.cur; total.b -= pads.words;
+        estimate_costs();
+    }
     void plan_pob(const PobParams& prm) {
         memset(&L, 0, sizeof L);
+        begin();
         L.circuit = 0; L.pob = prm; L.nkb = 0; max_stage = 0; L.decl_order = p.decl_order;
         L.fp_n2be32 = n2be_footprint(32); L.fp_n2beN = n2be_footprint(prm.amountBytes);
         // track 1 (TB): everything that hangs off the main inputs only -- range checks, Poseidons, BurnAddressHash, ProofOfWorkChecker,
@@ -1384,14 +1411,14 @@ struct Plan {
         }
         proof_of_work_checker(TB + 2);                         // :211 (inputs only; in step with BurnAddressHash so that the two sponges share their launches)
         unit(U_POB_FINAL, 10);
-        total = p.cur;
-        estimate_costs();
+        finish();
     }
     // A gadget-level main (gadget_mains.hpp; reference tests/test.py:146-201): template `tid` with parameters prm[0..nprm).  Returns null or
     // the reason the instantiation is refused.  Mains without a sponge are ONE unit (stage 1); the four Keccak mains are planned from the split
     // units of the production circuits, with the template's own input wires written from the packed inputs by a U_GM_INPUT unit first.
     const char* plan_gadget(uint32_t tid, const int* prm, int nprm) {
         memset(&L, 0, sizeof L);
+        begin();
         L.circuit = 2; L.nkb = 0; max_stage = 0; ntracks = 1; L.decl_order = p.decl_order;
         L.pob = PobParams{1, 1, 1, 0, 31, 0, fr_zero(), fr_zero()};
         L.fp_n2be32 = n2be_footprint(32); L.fp_n2beN = n2be_footprint(31);
@@ -1455,12 +1482,12 @@ struct Plan {
             L.gm.nfr_in = 3; L.gm.nsm_in = 1; L.gm.nout = 0;
         } else unit(U_GM, 1, tid, (uint32_t)a, (uint32_t)b, (uint32_t)c, (uint32_t)d);
         nfr_in = L.gm.nfr_in; nsm_in = L.gm.nsm_in;
-        total = p.cur;
-        estimate_costs();
+        finish();
         return nullptr;
     }
     void plan_spend(const SpendParams& prm) {
         memset(&L, 0, sizeof L);
+        begin();
         L.circuit = 1; L.spend = prm; L.nkb = 0; max_stage = 0; ntracks = 1; L.decl_order = p.decl_order;
         L.fp_n2be32 = n2be_footprint(32); L.fp_n2beN = n2be_footprint(prm.maxAmountBytes);
         L.pob = PobParams{1, 1, 1, 0, prm.maxAmountBytes, 0, fr_zero(), fr_zero()};
@@ -1473,7 +1500,6 @@ struct Plan {
         unit(U_SP_INPUT, 0);
         unit(U_SP_HEAD, 2);                                       // (the two Poseidon blocks: U_POS_WIDE units in stage 1)
         public_commitment(4, 3);
-        total = p.cur;
-        estimate_costs();
+        finish();
     }
 };

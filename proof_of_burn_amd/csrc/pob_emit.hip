@@ -102,7 +102,7 @@ static int emit_make_window(pob_ctx* h, uint32_t idx, uint64_t k, int slot) {
     A.emit_out = E.d_win[slot]; A.emit_sel = idx % 64; A.emit_group = idx / 64; A.emit_w0 = (uint32_t)w0; A.emit_wn = (uint32_t)wn;
     if (E.red) { A.emit_rbits = E.d_rbits; A.emit_rpre = E.d_rpre; }
     emit_units(h, A, k, launch_g_emit);
-    const u64* Gp = (const u64*)h->d_bits + (uint64_t)(idx / 64) * h->plan.total.b;
+    const u64* Gp = (const u64*)h->d_bits + (uint64_t)(idx / 64) * h->plan.bit_stride;
     for_each_run_piece(E, w0, wn, [&](const EmitState::Run& r, uint64_t lo, uint64_t hi) {       // the Keccak kernels' wires
         if (!E.red) {
             if (r.absorb) launch_k_emit_absorb(Gp, E.d_win[slot] + (lo - w0) * 32, AbsorbRef{r.b, r.prev, r.src}, r.o + (uint32_t)(lo - r.w), (uint32_t)(hi - lo), idx % 64, h->d_ktab, st);
@@ -530,7 +530,7 @@ static int group_make_window(pob_ctx* h, uint64_t k) {
     const uint32_t nblk = (uint32_t)((wn + 63) / 64);
     hipStream_t st = own_stream(h);
     HIPC(hipStreamWaitEvent(st, Gr.ev_free[ps], 0));                        // the copies of the window that used this packed slot before are done
-    const u64* Gp = (const u64*)h->d_bits + (uint64_t)Gr.group * h->plan.total.b;
+    const u64* Gp = (const u64*)h->d_bits + (uint64_t)Gr.group * h->plan.bit_stride;
     const GroupWin GW{Gr.d_win, Gr.plane, Gr.lanes, (uint32_t)w0, (uint32_t)wn, E.red ? E.d_rbits : nullptr, E.red ? E.d_rpre : nullptr};
     struct Piece { const EmitState::Run* r; uint64_t lo, hi; };
     std::vector<Piece> canon;                                               // what of the runs takes the canonical route, launched behind the fill

@@ -345,7 +345,7 @@ GArgs pob_detail::gargs(pob_ctx* h) {
     GArgs A; memset(&A, 0, sizeof A);
     A.units = h->d_units; A.order = h->d_order; A.L = h->d_L;
     A.bits = h->d_bits; A.sm = h->d_sm; A.fr = h->d_fr;
-    A.bits_stride = h->plan.total.b; A.sm_stride = (uint64_t)h->plan.total.s * 64; A.fr_stride = (uint64_t)h->plan.total.f * 512;
+    A.bits_stride = h->plan.bit_stride; A.sm_stride = (uint64_t)h->plan.total.s * 64; A.fr_stride = (uint64_t)h->plan.total.f * 512;
     A.pos_tab = h->d_pos; A.inv_lut = h->d_inv; A.pow256 = h->d_pow256; A.npow256 = h->npow256; A.in_fr = h->d_in_fr[h->in_cur]; A.in_sm = h->d_in_sm[h->in_cur];
     A.nfr_in = h->plan.nfr_in; A.nsm_in = h->plan.nsm_in;
     A.status = h->d_status_raw; A.chk_status = h->d_chk; A.bad_wire = h->d_bad; A.emit_counters = h->d_emit_ctr;
@@ -354,7 +354,7 @@ GArgs pob_detail::gargs(pob_ctx* h) {
 }
 static KArgs kargs(pob_ctx* h) {
     KArgs K; memset(&K, 0, sizeof K);
-    K.bits = (u64*)h->d_bits; K.group_stride = h->plan.total.b; K.sponges = h->d_sponges;
+    K.bits = (u64*)h->d_bits; K.group_stride = h->plan.bit_stride; K.sponges = h->d_sponges;
     K.perm_sponge = h->d_perm_sponge; K.perm_block = h->d_perm_block; K.bad_wire = h->d_bad;
     return K;
 }
@@ -403,19 +403,20 @@ static int make_plan(Plan& plan, std::string& err, int circuit, const uint64_t* 
         if (why) { err = std::string("gadget main: ") + why; return POB_E_ARG; }
     } else { err = "unknown circuit"; return POB_E_ARG; }
     const Cur t = plan.total;
-    if (t.b >= (1u << 29) || t.s >= (1u << 24) || t.f >= (1u << 21) || t.q >= (1u << 30)) {
+    if (plan.bit_stride >= (1u << 29) || t.s >= (1u << 24) || t.f >= (1u << 21) || t.q >= (1u << 30)) {
         err = "instantiation exceeds the layout's offset limits (BIT < 2^29, SM < 2^24, FR < 2^21 wires)"; return POB_E_ARG;
     }
     return POB_OK;
 }
 static void fill_info(const Plan& pl, uint32_t nperms, uint32_t max_batch, pob_info_t* info) {
     info->n_witness = pl.total.w; info->n_bit = pl.total.b; info->n_sm = pl.total.s; info->n_fr = pl.total.f;
+    info->bit_stride = pl.bit_stride;
     info->n_fr_inputs = pl.nfr_in; info->n_sm_inputs = pl.nsm_in; info->n_outputs = pl.L.circuit == 2 ? pl.L.gm.nout : 1;
     info->n_units = (uint32_t)pl.units.size(); info->n_sponges = (uint32_t)pl.sponges.size(); info->n_perms = nperms;
     { std::vector<char> used(pl.max_stage + 1, 0); for (const UnitDesc& u : pl.units) if (u.flags & UNIT_GEN) used[u.stage] = 1; for (const SpongeDesc& s : pl.sponges) used[s.stage] = 1;
       info->n_stages = 0; for (char c : used) info->n_stages += c; }
     info->max_batch = max_batch;
-    info->group_bytes = (uint64_t)pl.total.b * 8 + (uint64_t)pl.total.s * 256 + (uint64_t)pl.total.f * 2048;      // (derived wires take no storage)
+    info->group_bytes = (uint64_t)pl.bit_stride * 8 + (uint64_t)pl.total.s * 256 + (uint64_t)pl.total.f * 2048;      // (derived wires take no storage)
     info->n_derived = pl.total.q;
     info->n_alias = (uint64_t)nperms * ABSORB_ALIAS;
     info->kchk_rounds = (uint32_t)pob_kchk_rounds(); info->kgc_rounds = (uint32_t)pob_kgc_rounds();
@@ -634,7 +635,7 @@ int pob_open(int device, int circuit, const uint64_t* params, int nparams, uint3
     }
     h->stream3 = p_track1;
     const uint64_t G = h->groups, npad = G * 64;
-    HIPC(hipMalloc(&h->d_bits, G * (uint64_t)std::max(pl.total.b, 1u) * 8));
+    HIPC(hipMalloc(&h->d_bits, G * (uint64_t)std::max(pl.bit_stride, 1u) * 8));
     HIPC(hipMalloc(&h->d_sm, G * (uint64_t)std::max(pl.total.s, 1u) * 256));
     HIPC(hipMalloc(&h->d_fr, G * (uint64_t)std::max(pl.total.f, 1u) * 2048));
     HIPC(hipMalloc(&h->d_units, pl.units.size() * sizeof(UnitDesc)));
@@ -1261,7 +1262,7 @@ int pob_debug_store_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
     if (!h->inorder || !h->gc) { h->err = "pob_debug_store_fault: the calculator's generation carries no evaluation (pob_set_inorder bit 2)"; return POB_E_STATE; }
     bool found = false;
     if (cls == POB_CLASS_BIT) {
-        if (index >= h->plan.total.b) return POB_E_ARG;
+        if (index >= h->plan.bit_stride) return POB_E_ARG;      // (ranks run over the padded slab; a padding word is no sponge's and no unit's: armed below without a wire, and nothing stores it)
         for (const SpongeDesc& sp : h->plan.sponges) {
             if (index < sp.abs_b || index >= sp.abs_b + (uint64_t)sp.n * ABSORB_BITS) continue;
             const uint32_t b = (uint32_t)((index - sp.abs_b) / ABSORB_BITS), o = (uint32_t)((index - sp.abs_b) % ABSORB_BITS);
@@ -1278,7 +1279,7 @@ int pob_debug_store_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
     h->fault_g = !found;
     if (!found) {
         const Cur t = h->plan.total;
-        if (!(h->circuit == POB_CIRCUIT_PROOF_OF_BURN || h->circuit == POB_CIRCUIT_SPEND) || (cls == POB_CLASS_BIT ? index >= t.b : cls == POB_CLASS_SM ? index >= t.s : cls == POB_CLASS_FR ? index >= t.f : true)) {
+        if (!(h->circuit == POB_CIRCUIT_PROOF_OF_BURN || h->circuit == POB_CIRCUIT_SPEND) || (cls == POB_CLASS_BIT ? index >= h->plan.bit_stride : cls == POB_CLASS_SM ? index >= t.s : cls == POB_CLASS_FR ? index >= t.f : true)) {
             h->err = "pob_debug_store_fault: not a stored word whose evaluation rides with its generation"; return POB_E_ARG;
         }
         if (wire) *wire = 0xFFFFFFFFu;
@@ -1291,7 +1292,7 @@ int pob_debug_value_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
     if (!h || group >= h->groups) return POB_E_ARG;
     if (!h->inorder || !h->gc) { h->err = "pob_debug_value_fault: the calculator's generation carries no evaluation (pob_set_inorder bit 2)"; return POB_E_STATE; }
     const Cur t = h->plan.total;
-    if (!(cls == POB_CLASS_BIT ? index < t.b : cls == POB_CLASS_SM ? index < t.s : cls == POB_CLASS_FR ? index < t.f : false)) { h->err = "pob_debug_value_fault: no such word"; return POB_E_ARG; }
+    if (!(cls == POB_CLASS_BIT ? index < h->plan.bit_stride : cls == POB_CLASS_SM ? index < t.s : cls == POB_CLASS_FR ? index < t.f : false)) { h->err = "pob_debug_value_fault: no such word"; return POB_E_ARG; }
     auto refuse = [&](const char* why) { h->err = std::string("pob_debug_value_fault: not covered: ") + why; return POB_E_ARG; };
     if (!(h->circuit == POB_CIRCUIT_PROOF_OF_BURN || h->circuit == POB_CIRCUIT_SPEND)) return refuse("the G units of a gadget-level main do not ride");
     if (cls == POB_CLASS_BIT) return refuse("BIT words (round blocks, sponge chains, the G units' bit runs)");
@@ -1327,10 +1328,10 @@ int pob_debug_value_fault(pob_handle h, int cls, uint32_t group, uint64_t index,
 }
 
 int pob_debug_xor_bits(pob_handle h, uint32_t group, uint64_t bit_index, uint64_t mask) {
-    if (!h || group >= h->groups || bit_index >= h->plan.total.b) return POB_E_ARG;
+    if (!h || group >= h->groups || bit_index >= h->plan.bit_stride) return POB_E_ARG;      // (a padding word is a word of the slab: flipped like any other, no kernel reads it)
     HIPC(hipSetDevice(h->device));
     h->rode = false;
-    hipLaunchKernelGGL(k_xor_word, dim3(1), dim3(1), 0, own_stream(h), h->d_bits + (uint64_t)group * h->plan.total.b + bit_index, mask);
+    hipLaunchKernelGGL(k_xor_word, dim3(1), dim3(1), 0, own_stream(h), h->d_bits + (uint64_t)group * h->plan.bit_stride + bit_index, mask);
     HIPC(hipStreamSynchronize(own_stream(h)));
     return POB_OK;
 }
@@ -1341,8 +1342,8 @@ int pob_debug_poke(pob_handle h, int cls, uint32_t group, uint64_t index, uint32
     h->rode = false;
     const Cur t = h->plan.total;
     if (cls == POB_CLASS_BIT) {
-        if (index >= t.b) return POB_E_ARG;
-        hipLaunchKernelGGL(k_xor_word, dim3(1), dim3(1), 0, own_stream(h), h->d_bits + (uint64_t)group * t.b + index, (uint64_t)(xor_mask & 1u) << lane);
+        if (index >= h->plan.bit_stride) return POB_E_ARG;
+        hipLaunchKernelGGL(k_xor_word, dim3(1), dim3(1), 0, own_stream(h), h->d_bits + (uint64_t)group * h->plan.bit_stride + index, (uint64_t)(xor_mask & 1u) << lane);
     } else if (cls == POB_CLASS_SM) {
         if (index >= t.s) return POB_E_ARG;
         hipLaunchKernelGGL(k_xor_u32, dim3(1), dim3(1), 0, own_stream(h), (uint32_t*)h->d_sm + ((uint64_t)group * t.s + index) * 64 + lane, xor_mask);
@@ -1407,6 +1408,10 @@ int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t
         if (k >= L.nkb) return POB_E_ARG;
         const KBRefs& r = L.kbs[k];
         return n == "kb.inBlocks" ? set(POB_CLASS_BIT, r.inBlocks.i, r.inBlocks.w) : set(POB_CLASS_BIT, r.abs_b + AB_MID, r.abs_w);
+    }
+    if (n == "bit.pad") {                                 // the k-th run of padding words of the BIT slab (policy.hpp align_bits), in rank order: *index = its first rank, *wire = its length in words (no wire has them)
+        if (k >= pl.pads.n) return POB_E_ARG;
+        return set(POB_CLASS_BIT, pl.pads.at[k], pl.pads.len[k]);
     }
     if (n == "pad.div.out" || n == "pad.div.rem") {       // of KeccakBytes instance k
         if (k >= L.nkb) return POB_E_ARG;

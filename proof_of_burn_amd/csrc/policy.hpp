@@ -78,6 +78,7 @@ enum : uint32_t {
 static inline uint32_t pob_decl_order_env() { static const uint32_t v = (getenv("POB_DECL_ORDER") && getenv("POB_DECL_ORDER")[0] == '1') ? 1u : 0u; return v; }
 #define POB_DECL_ORDER_DEFAULT pob_decl_order_env()
 #endif
+#define BIT_ALIGN 16u      // BIT words per 128-byte line
 struct PolBase {
     Cur cur;
     uint32_t decl_order = POB_DECL_ORDER_DEFAULT;
@@ -86,6 +87,12 @@ struct PolBase {
     HD uint32_t dvs(uint32_t n) { const uint32_t w = cur.w; cur.w += n; cur.q += n; return w; }     // n derived wires: no storage, the first one's wire index
     HD FrRef frs(uint32_t n) { FrRef r = {cur.w, cur.f}; cur.w += n; cur.f += n; return r; }
     HD void skip_alias(uint32_t nw, uint32_t nb) { cur.w += nw; cur.b += nb; }       // nw wires of which nb are stored BIT wires, the rest aliases of them (Absorb blocks, circuits.hpp)
+    // LINE ALIGNMENT of the Keccak storage: the next BIT rank becomes a multiple of BIT_ALIGN words (one 128-byte line).  The ranks skipped are PADDING: no wire has them,
+    // nothing reads or writes them.  Taken ahead of every array that the sponge kernels access as 512-byte wave-wide rows -- KeccakBytes.inBlocks and a sponge's first Absorb
+    // block (circuits.hpp kb_head / kb_declare_keccak); every offset inside a sponge is a multiple of 16 words, so with a group stride that is one too (Plan::bit_stride)
+    // every such row covers four whole lines in every group.  A function of the absolute rank only: every policy that reaches the step from the same cursor takes the same one.
+    // ahead: the step is taken `ahead` stored BIT wires before the array it aligns (the rank behind the next `ahead` ranks becomes the multiple).
+    HD uint32_t align_bits(uint32_t ahead = 0) { const uint32_t pad = (0u - (cur.b + ahead)) & (BIT_ALIGN - 1u); cur.b += pad; return pad; }
 };
 
 // ------------------------------------------------------------------ host-side layout planner policy
@@ -94,12 +101,21 @@ struct PolBase {
 enum : uint32_t { NOTE_POSEIDON = 1, NOTE_N2BE = 2, NOTE_SHIFTRIGHT = 3, NOTE_SHIFTLEFT = 4 };
 struct PlanNote { uint32_t what, n; Cur cur; uint32_t a[7]; };
 #define PLAN_MAX_NOTES 8
+// the runs of padding words the planner's own walk took (PolBase::align_bits): first rank, words.  Two per KeccakBytes instance at most (circuits.hpp MAX_KB) + the slab's end
+#define BIT_PAD_MAX 160
+struct PadLog { uint32_t n, words, at[BIT_PAD_MAX], len[BIT_PAD_MAX]; };
 struct CountP : PolBase {
     static constexpr bool is_gen = false, is_check = false, is_emit = false, is_count = true, ride = false;
     uint32_t nput = 0;    // wires written: the planner's cost estimate of a unit (long units are dispatched first)
     uint32_t nb = 0, ns = 0, nf = 0;      // ... by storage class (tools/plan_stats.cpp)
     PlanNote notes[PLAN_MAX_NOTES]; uint32_t nnotes = 0;
     bool notes_overflow = false;          // a composite with more split sub-blocks than the table holds: the planner refuses the plan (Plan::take_notes)
+    PadLog* pads = nullptr;               // the planner's policy: where its walk padded the BIT cursor (scratch walks over the same wires: null)
+    HD uint32_t align_bits(uint32_t ahead = 0) {
+        const uint32_t at = cur.b, n = PolBase::align_bits(ahead);
+        if (pads && n) { if (pads->n < BIT_PAD_MAX) { pads->at[pads->n] = at; pads->len[pads->n] = n; } pads->n++; pads->words += n; }
+        return n;
+    }
     HD void note(uint32_t what, uint32_t n, Cur c, uint32_t a0 = 0, uint32_t a1 = 0, uint32_t a2 = 0, uint32_t a3 = 0, uint32_t a4 = 0, uint32_t a5 = 0, uint32_t a6 = 0) {
         if (nnotes >= PLAN_MAX_NOTES) { notes_overflow = true; return; }
         PlanNote& x = notes[nnotes++]; x.what = what; x.n = n; x.cur = c;

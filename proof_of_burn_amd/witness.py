@@ -116,7 +116,8 @@ class PobInfo(ctypes.Structure):
                 ("n_units", ctypes.c_uint32), ("n_sponges", ctypes.c_uint32), ("n_perms", ctypes.c_uint32),
                 ("n_stages", ctypes.c_uint32), ("max_batch", ctypes.c_uint32),
                 ("group_bytes", ctypes.c_uint64), ("keccak_bit_wires", ctypes.c_uint64), ("n_derived", ctypes.c_uint64), ("n_alias", ctypes.c_uint64),
-                ("kchk_rounds", ctypes.c_uint32), ("kgc_rounds", ctypes.c_uint32)]
+                ("kchk_rounds", ctypes.c_uint32), ("kgc_rounds", ctypes.c_uint32),
+                ("bit_stride", ctypes.c_uint64)]      # 8-byte words between two groups' BIT slabs: n_bit + the alignment padding, a multiple of 16 (include/pob_hip.h)
 
 
 # one result record (include/pob_hip.h POB_RECORD_BYTES = 44)
