@@ -420,6 +420,11 @@ int pob_debug_fr_inv(int device, const uint8_t* in, uint32_t n, uint8_t* out_kal
 /* Test hook: fr_sqr(a) and fr_mul(a, a) of the device code on n 32-byte LE values a < p (Montgomery products: a * a * 2^-256 mod p); the two must be
  * bit-equal.                                                                                                                          */
 int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr, uint8_t* out_mul);
+/* Test hook: ONE operation of the device code's field arithmetic on n operands (pairs), 32-byte LE each, RAW limbs in and out -- no conversion inside, every
+ * operand < p.  MUL / MUL_INL: the called and the inlined Montgomery product a * b * 2^-256; ADD, SUB, NEG: a + b, a - b, -a; TO_MONT / FROM_MONT: a * 2^256 /
+ * a * 2^-256; FROM_I64: the low 8 bytes of a as a signed value k (not INT64_MIN) -> k * 2^256.  All mod p.  b may be null for the unary operations.        */
+enum { POB_FR_OP_MUL = 0, POB_FR_OP_MUL_INL = 1, POB_FR_OP_ADD = 2, POB_FR_OP_SUB = 3, POB_FR_OP_NEG = 4, POB_FR_OP_TO_MONT = 5, POB_FR_OP_FROM_MONT = 6, POB_FR_OP_FROM_I64 = 7 };
+int pob_debug_fr_ops(int device, int op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out);
 /* Test hook: storage class, rank within the class and wire index of a few named wires: "commitment"; "poseidon" (k-th wire of the
  * first Poseidon block), "poseidon.t3" / ".t4" / ".t5" (... of the first Poseidon block of width T = 3 / 4 / 5); "pad.div.out" / "pad.div.rem" of KeccakBytes instance k (the Divide hint of divide.circom:23-24); ProofOfBurn only: "sc.exists" [k] of layer 1's SubstringCheck. */
 int pob_debug_ref(pob_handle h, const char* name, uint32_t k, int* cls, uint64_t* index, uint64_t* wire);      /* also "kb.inLen": inLen of KeccakBytes instance k; "kb.inBlocks": its first inBlocks bit; "kb.absorb": the first stored word (midRound[0][0][0]) and the first wire of its first Absorb block; "bit.pad": the k-th run of padding words of the BIT slab (pob_info_t.bit_stride), *index = its first rank, *wire = its length in words */

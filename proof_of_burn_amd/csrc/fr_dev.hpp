@@ -246,8 +246,9 @@ HD void fr256_submod(uint32_t* a, const uint32_t* b) {   // a <- a - b mod p
         for (int i = 0; i < 8; i++) { c += (uint64_t)a[i] + P[i]; a[i] = (uint32_t)c; c >>= 32; }
     }
 }
-#if defined(__HIP_DEVICE_COMPILE__)
-// Device: Kaliski's almost-inverse with batched shifts, branch-free per step.  Phase 1 works on plain 256-bit integers --
+#if defined(__HIP_DEVICE_COMPILE__) || defined(POB_HOSTSIM)
+// Device (and the tests' host build of the kernels, where k_fr_inv_test alone calls it: a wavefront meets in the loop, which makes no sense outside a kernel):
+// Kaliski's almost-inverse with batched shifts, branch-free per step.  Phase 1 works on plain 256-bit integers --
 // (u, v) start as (p, x), the coefficients (r, s) are only added and shifted LEFT (no modular halving), k counts the shifts --
 // and ends with r = -x^-1 * 2^k mod p, 254 <= k <= 508.  Every step subtracts the smaller of the two odd values from the larger
 // and strips ALL trailing zeros of the difference at once (ctz), so ~190 steps of ~120 instructions replace the ~360 steps of
@@ -255,9 +256,7 @@ HD void fr256_submod(uint32_t* a, const uint32_t* b) {   // a <- a - b mod p
 // 2^(768-k) from a table: (x = a*R)  x^-1 * 2^k * 2^(768-k) * 2^-256 = a^-1 * R.
 #include "fr_pow2_table.h"
 static __device__ const uint32_t FR_POW2_TAB[FR_POW2_TAB_LEN * 8] = FR_POW2_TAB_INIT;
-// fr_inv_inl: the inlined form -- as a called function it needs more VGPRs than the caller-saved set and saves callee-saved ones on the
-// stack; fr_inv: the called form.  (Round 4: only the emitter inverts -- every IsZero.inv wire is derived -- and the inversion test kernel.)
-HD Fr fr_inv_inl(Fr a) {
+HD Fr fr_inv_kaliski_inl(Fr a) {
     const uint32_t P[8] = FR_P_LIMBS;
     uint32_t u[8], v[8], r[8], s[8];
 #pragma unroll
@@ -307,13 +306,20 @@ HD Fr fr_inv_inl(Fr a) {
         const bool gt = !bw && nzd != 0;     // u > v: u <- d >> t, r <- r + s, s <<= t;  otherwise v <- d >> t, s <- r + s, r <<= t
         const uint32_t t = nzd ? (d[0] ? (uint32_t)__builtin_ctz(d[0]) : 31u) : 1u;
         const uint32_t tt = t > 31u ? 31u : t;                   // >= 1: the difference of two odd values is even
+        // a lane that is done or idle runs this step too, on an odd u - v: tt = 0, its result is dropped.  The device takes a shift count mod 32; in C++ a count of 32
+        // is undefined, and the tests' host build runs under UBSan: masked there (on the device the mask is a different instruction sequence for the same values)
+#ifdef POB_HOSTSIM
+        const uint32_t ct = (32u - tt) & 31u;
+#else
+        const uint32_t ct = 32u - tt;
+#endif
         uint32_t dsh[8], sh[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const uint32_t hi_ = i < 7 ? d[i + 1] : 0u;
-            dsh[i] = (d[i] >> tt) | (hi_ << (32 - tt));
+            dsh[i] = (d[i] >> tt) | (hi_ << ct);
             const uint32_t ci = gt ? s[i] : r[i], cl = i > 0 ? (gt ? s[i - 1] : r[i - 1]) : 0u;
-            sh[i] = (ci << tt) | (cl >> (32 - tt));
+            sh[i] = (ci << tt) | (cl >> ct);
         }
         if (active) {
 #pragma unroll
@@ -337,6 +343,11 @@ HD Fr fr_inv_inl(Fr a) {
     Fr y = fr_mul(res, c);
     return fr_is_zero(a) ? fr_zero() : y;
 }
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+// fr_inv_inl: the inlined form -- as a called function it needs more VGPRs than the caller-saved set and saves callee-saved ones on the
+// stack; fr_inv: the called form.  (Round 4: only the emitter inverts -- every IsZero.inv wire is derived -- and the inversion test kernel.)
+HD Fr fr_inv_inl(Fr a) { return fr_inv_kaliski_inl(a); }
 HDN Fr fr_inv(Fr a) { return fr_inv_inl(a); }
 // a^(p-2) by square-and-multiply over fr_mul calls only (no stack): the emitter's rare path (IsZero operands beyond the table)
 HD Fr fr_inv_fermat(const Fr& a) {

@@ -144,8 +144,32 @@ __global__ void k_fr_inv_test(const uint32_t* in, uint32_t* out_kaliski, uint32_
     if (t >= n) return;
     Fr c; for (int j = 0; j < 8; j++) c.l[j] = in[t * 8 + j];
     const Fr x = fr_to_mont(c);
-    const Fr a = fr_is_zero(x) ? fr_zero() : fr_from_mont(fr_inv(x)), b = fr_is_zero(x) ? fr_zero() : fr_from_mont(fr_inv_fermat(x));
+#ifdef POB_HOSTSIM
+    const Fr ix = fr_inv_kaliski_inl(x);           // the tests' host build: the device's body (every thread of the wavefront calls it: it meets in its loop), where fr_inv is the planner's Euclid
+#else
+    const Fr ix = fr_inv(x);
+#endif
+    const Fr a = fr_is_zero(x) ? fr_zero() : fr_from_mont(ix), b = fr_is_zero(x) ? fr_zero() : fr_from_mont(fr_inv_fermat(x));
     for (int j = 0; j < 8; j++) { out_kaliski[t * 8 + j] = a.l[j]; out_fermat[t * 8 + j] = b.l[j]; }
+}
+// test hook (pob_debug_fr_ops): one operation of fr_dev.hpp on n operand pairs, raw limbs in and out (no conversion: what the operation's own domain is, is the caller's business)
+__global__ void k_fr_ops_test(int op, const uint32_t* a_in, const uint32_t* b_in, uint32_t* out, uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    Fr a, b = fr_zero(), r = fr_zero();
+    for (int j = 0; j < 8; j++) a.l[j] = a_in[(size_t)t * 8 + j];
+    if (op <= POB_FR_OP_SUB) for (int j = 0; j < 8; j++) b.l[j] = b_in[(size_t)t * 8 + j];       // the binary operations
+    switch (op) {
+        case POB_FR_OP_MUL: r = fr_mul(a, b); break;
+        case POB_FR_OP_MUL_INL: r = fr_mul_inl(a, b); break;
+        case POB_FR_OP_ADD: r = fr_add(a, b); break;
+        case POB_FR_OP_SUB: r = fr_sub(a, b); break;
+        case POB_FR_OP_NEG: r = fr_neg(a); break;
+        case POB_FR_OP_TO_MONT: r = fr_to_mont(a); break;
+        case POB_FR_OP_FROM_MONT: r = fr_from_mont(a); break;
+        case POB_FR_OP_FROM_I64: r = fr_from_i64((int64_t)((uint64_t)a.l[0] | ((uint64_t)a.l[1] << 32))); break;
+    }
+    for (int j = 0; j < 8; j++) out[(size_t)t * 8 + j] = r.l[j];
 }
 // test hook (pob_debug_fr_sqr): the device's Montgomery square and product of a value with itself on n inputs < p
 __global__ void k_fr_sqr_test(const uint32_t* in, uint32_t* out_sqr, uint32_t* out_mul, uint32_t n) {
@@ -1385,6 +1409,23 @@ int pob_debug_fr_sqr(int device, const uint8_t* in, uint32_t n, uint8_t* out_sqr
         if (hipMemcpy(out_sqr, d_a, bytes, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(out_mul, d_b, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = POB_OK;
     }
     if (d_in) hipFree(d_in); if (d_a) hipFree(d_a); if (d_b) hipFree(d_b);
+    return rc;
+}
+
+// one operation of the device's field arithmetic (POB_FR_OP_*) on n pairs of 32-byte LE operands, raw limbs in and out; b may be null for the unary operations
+int pob_debug_fr_ops(int device, int op, const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out) {
+    if (!a || !out || n == 0 || op < 0 || op > POB_FR_OP_FROM_I64 || (op <= POB_FR_OP_SUB && !b)) return POB_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return POB_E_HIP;
+    uint32_t *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
+    const size_t bytes = (size_t)n * 32;
+    const bool binary = op <= POB_FR_OP_SUB;
+    int rc = POB_E_HIP;
+    if (hipMalloc(&d_a, bytes) == hipSuccess && hipMalloc(&d_o, bytes) == hipSuccess && (!binary || hipMalloc(&d_b, bytes) == hipSuccess) &&
+        hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice) == hipSuccess && (!binary || hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice) == hipSuccess)) {
+        hipLaunchKernelGGL(k_fr_ops_test, dim3((n + 63) / 64), dim3(64), 0, 0, op, d_a, d_b, d_o, n);
+        if (hipMemcpy(out, d_o, bytes, hipMemcpyDeviceToHost) == hipSuccess) rc = POB_OK;
+    }
+    if (d_a) hipFree(d_a); if (d_b) hipFree(d_b); if (d_o) hipFree(d_o);
     return rc;
 }
 

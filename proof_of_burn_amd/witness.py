@@ -218,6 +218,8 @@ def load_library() -> ctypes.CDLL:
     lib.pob_emit_selfcheck_result.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     lib.pob_debug_fr_inv.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, vp, vp]
     lib.pob_debug_fr_sqr.argtypes = [ctypes.c_int, vp, ctypes.c_uint32, vp, vp]
+    if hasattr(lib, "pob_debug_fr_ops"):          # (an older build named by POB_LIB_PATH, as above)
+        lib.pob_debug_fr_ops.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint32, vp]
     lib.pob_debug_ref.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.pob_keccak256.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
     lib.pob_keccak256.restype = None
@@ -233,7 +235,7 @@ EXPORTED_SYMBOLS = ["pob_plan_info", "pob_gadget_template", "pob_open", "pob_clo
                     "pob_upload_inputs8", "pob_upload_inputs8_async", "pob_narrow_inputs", "pob_pack_json_batch8",
                     "pob_results_fetch", "pob_results_wait", "pob_emit_begin_reduced", "pob_reduced_map_pin", "pob_write_wtns_reduced", "pob_emit_measure_ex", "pob_generate",
                     "pob_constraint_check", "pob_sync", "pob_set_partner", "pob_results", "pob_results_device", "pob_results_records_device", "pob_gather_records", "pob_emit_witness",
-                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_emit_group_selfcheck", "pob_emit_group_selfcheck_result", "pob_debug_selfcheck_sites", "pob_debug_group_emit_xor", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_set_audit", "pob_audit_last", "pob_debug_value_fault", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
+                    "pob_write_wtns", "pob_emit_begin", "pob_emit_next", "pob_emit_queue", "pob_emit_measure", "pob_emit_begin_packed", "pob_emit_next_packed", "pob_unpack_window", "pob_write_wtns_packed", "pob_emit_measure_packed", "pob_emit_begin_group_packed", "pob_emit_next_group_packed", "pob_write_wtns_group", "pob_emit_measure_group", "pob_emit_group_selfcheck", "pob_emit_group_selfcheck_result", "pob_debug_selfcheck_sites", "pob_debug_group_emit_xor", "pob_time_kernel", "pob_probe_check_kernel", "pob_debug_xor_bits", "pob_debug_store_fault", "pob_debug_stream_create", "pob_debug_stream_destroy", "pob_debug_poke", "pob_debug_ref", "pob_debug_emit_counters", "pob_debug_fr_inv", "pob_debug_fr_sqr", "pob_debug_fr_ops", "pob_emit_selfcheck", "pob_emit_selfcheck_alias", "pob_emit_selfcheck_result", "pob_set_inorder", "pob_set_audit", "pob_audit_last", "pob_debug_value_fault", "pob_keccak256", "pob_pow_search", "pob_pow_search_gpu"]
 
 
 def plan_info(main: str) -> PobInfo:
